@@ -8,7 +8,9 @@ SAME frame (strong scaling: the frame is fixed, rows are split), then the tiles
 are gathered to rank 0 over RCCL (torch.distributed "nccl") and un-interleaved by
 a HIP kernel.  A step = one full frame including the gather.
 
-    python bench.py                       # N=1, defaults finish in about a minute
+    python bench.py                       # N=1: set-up, warm-up, the timed steps, the line
+    python bench.py --full                # also the secondary legs (below), some 10 s more
+    python bench.py --dump-outputs DIR    # writes the last timed frame as DIR/frame.npy
     torchrun --nproc-per-node 8 bench.py --gpus 8
     python bench.py --gpus 8              # the same: starts torch.distributed.run itself
     python bench.py --gpus 8 --single-process
@@ -20,7 +22,14 @@ equal N, and N ranks on the RCCL backend need N visible GPUs; anything else exit
 with status 2 (--stack-ranks allows more ranks than GPUs, for rehearsals only).
 
 Prints ONE JSON line on rank 0.  `value` = traced ray segments of the whole frame
-(all ranks) / max-over-ranks wall time of the timed steps.
+(all ranks) / max-over-ranks wall time of the timed steps; `ms_per_step` = that wall
+time over --steps, in milliseconds.
+
+A plain run does only what the headline needs.  --full adds, after the timed steps
+and outside them: the executed-work counting frame (roofline.achieved on executed
+work rather than the brute-force count), the CPU baseline, the draw_frame leg and the
+side scenes (N = 1).  --no-cpu-baseline, --no-count-work, --no-draw-frame and
+--side-scenes '' drop single legs of a --full run.
 """
 from __future__ import annotations
 
@@ -61,10 +70,18 @@ def parse():
                     help="row-band weighting of an N-rank frame, CYCLE:SKIP: rank 0, which also receives the "
                          "gather and assembles, sits out SKIP of every CYCLE rounds of bands; 'auto' = "
                          "wololo.default_band(N), '0:0' = one band per rank and round")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs after the timed steps: executed-work counting frame, CPU "
+                         "baseline, draw_frame leg, side scenes (each has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last timed step produced as DIR/frame.npy "
+                         "(float32, H x W x 4; a fixed seeded sample of its pixels, (n, 4), with their flat pixel "
+                         "indices in DIR/frame_pixels.npy, when the frame exceeds the 64 MB limit)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-count-work", action="store_true",
-                    help="skip the executed-work counting frame (roofline.achieved then uses the brute-force count)")
+                    help="--full: skip the executed-work counting frame (roofline.achieved then uses the brute-force "
+                         "count, as in a plain run)")
     ap.add_argument("--tracer", default=os.environ.get("WOLOLO_TRACER", "auto"),
                     choices=["auto", "interpreter", "jit", "lanes"],
                     help="path-tracer kernel (renderer_ext.h Wo_Tracer); results are identical")
@@ -94,12 +111,35 @@ def parse():
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="per-dispatch HBM bytes measured by rocprofv3 --pmc (profiles/*.json) for roofline.traffic")
     ap.add_argument("--side-scenes", default="csg32_nested",
-                    help="N=1 csg32 runs only: comma-separated scenes measured after the headline in the same "
+                    help="--full, N=1 csg32 runs only: comma-separated scenes measured after the headline in the same "
                          "invocation and reported as sub-objects of the line ('' = none)")
     ap.add_argument("--no-draw-frame", action="store_true",
-                    help="N=1: skip the draw_frame leg (wo_renderer_draw_frame frames, map-back included)")
+                    help="--full, N=1: skip the draw_frame leg (wo_renderer_draw_frame frames, map-back included)")
     ap.add_argument("--draw-frames", type=int, default=60, help="frames of the draw_frame leg")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_count_work = args.no_draw_frame = True
+        args.side_scenes = ""
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, frame) -> None:
+    """--dump-outputs: the frame of the last timed step (host float32 array, H x W x 4) as
+    DIR/frame.npy.  A frame over the limit is sampled: the same pixels every run (seed 0),
+    in ascending order, their flat indices (y * W + x) beside them as float64."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes > DUMP_LIMIT_BYTES:
+        px = frame.reshape(-1, frame.shape[-1])
+        n = DUMP_LIMIT_BYTES // (px.shape[1] * 4 + 8) * 3 // 4
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+        np.save(os.path.join(dirname, "frame_pixels.npy"), idx.astype(np.float64))
+        frame = px[idx]
+    np.save(os.path.join(dirname, "frame.npy"), frame)
 
 
 def fail(msg: str, code: int = 2):
@@ -314,11 +354,15 @@ def main():
             print(f"[bench] work counters traced {work['segments']} segments, the timed frames "
                   f"{segs_local / args.steps}", file=sys.stderr)
 
+    got = None
+    if rank == 0 and (args.verify or args.dump_outputs):
+        got = (frame if world > 1 else outs[(frame_no[0] - 1) % len(outs)][:H]).cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, got)
     verified = None
     if args.verify and rank == 0:
         import numpy as np
         full = r.render(params)
-        got = (frame if world > 1 else outs[(frame_no[0] - 1) % len(outs)][:H]).cpu().numpy()
         verified = bool(np.array_equal(got, full))
         if not verified:
             bad = int((got != full).any(axis=-1).sum())
@@ -608,6 +652,8 @@ def single_process(args):
     segs = r.take_segments()
     peers = sorted({r.peer_mode(i) for i in range(1, n)}) if n > 1 else []
     last = frames[(fno[0] - 1) & 1].cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     r.set_devices(1)  # the counting frame and the verification render run on one rank
     work = None
     if info.mode == wl.MODE_PATHTRACE and not args.no_count_work:

@@ -46,6 +46,61 @@ def test_single_process_too_few_gpus_exits_2():
     assert p.returncode == 2 and "needs 2 GPUs" in p.stderr, p.stderr[-2000:]
 
 
+def _parse(argv, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    return bench.parse()
+
+
+def test_plain_run_leaves_the_secondary_legs_out(monkeypatch):
+    """Without --full every leg beyond the timed steps is off, whatever else is given;
+    --steps and --warmup are taken as given."""
+    a = _parse(["--gpus", "1", "--steps", "7", "--warmup", "2"], monkeypatch)
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu_baseline and a.no_count_work and a.no_draw_frame and a.side_scenes == ""
+    a = _parse(["--side-scenes", "csg32_nested"], monkeypatch)
+    assert a.side_scenes == ""
+
+
+def test_full_run_keeps_the_secondary_legs_and_their_switches(monkeypatch):
+    a = _parse(["--full"], monkeypatch)
+    assert a.full and not (a.no_cpu_baseline or a.no_count_work or a.no_draw_frame)
+    assert a.side_scenes == "csg32_nested"
+    a = _parse(["--full", "--no-cpu-baseline", "--side-scenes", ""], monkeypatch)
+    assert a.no_cpu_baseline and not a.no_count_work and a.side_scenes == ""
+
+
+def test_dump_outputs_writes_the_frame(tmp_path):
+    """A frame within the limit is written whole, as float32."""
+    np = pytest.importorskip("numpy")
+    sys.path.insert(0, ROOT)
+    import bench
+    frame = np.arange(5 * 7 * 4, dtype=np.float32).reshape(5, 7, 4)
+    bench.dump_outputs(str(tmp_path / "out"), frame)
+    assert sorted(os.listdir(tmp_path / "out")) == ["frame.npy"]
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+
+
+def test_dump_outputs_samples_a_frame_over_the_limit(tmp_path, monkeypatch):
+    """Over the limit: the same pixels every time, in order, with their indices, and the
+    files together stay under the limit."""
+    np = pytest.importorskip("numpy")
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    frame = np.random.default_rng(5).random((33, 17, 4), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    px, idx = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_pixels.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and px.shape == (len(idx), 4)
+    assert 0 < len(idx) < 33 * 17 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(px, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_pixels.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 4096
+
+
 @pytest.mark.parametrize("n", [2, 8])
 def test_self_launch_starts_n_ranks(n, monkeypatch):
     """The command bench starts without a launcher: torch.distributed.run, N processes

@@ -84,6 +84,26 @@ def test_self_launch_without_a_launcher():
     assert line["verified_vs_full_render"] is True
 
 
+def test_plain_run_is_lean_and_dumps_its_last_frame(tmp_path):
+    """`bench.py --gpus 1` without --full: the line carries the headline and none of the
+    secondary legs, the timed step count is --steps, and --dump-outputs writes the last
+    timed frame, which --verify finds equal to a full render bit for bit."""
+    import numpy as np
+    out = tmp_path / "dump"
+    line = _bench_line([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "480",
+                        "--height", "270", "--spp", "8", "--verify", "--dump-outputs", str(out)])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["ms_per_step"] > 0 and line["unit"] == "Mrays/s" and line["dtype"] == "f32"
+    # ms_per_step is printed to 1 us; a step of this frame takes well over 20 us
+    assert line["value"] == pytest.approx(line["segments_per_frame"] / line["ms_per_step"] / 1e3, rel=0.05)
+    assert line["cpu_baseline"] is None and "draw_frame" not in line and "nested" not in line
+    assert "executed_flop_per_segment" not in line["roofline"]
+    assert line["verified_vs_full_render"] is True
+    frame = np.load(out / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (270, 480, 4)
+    assert np.isfinite(frame).all() and frame[..., :3].max() > 0
+
+
 def test_rank_mismatch_fails_loudly():
     """--gpus 2 on one GPU without --stack-ranks: exit status 2 before any rank starts."""
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + SMALL, cwd=ROOT, capture_output=True,
