@@ -100,8 +100,21 @@ typedef struct Gen {
     const struct RTree* rtree; /* collect over the CSG tree with relevance-box culls (gen_rtree), or NULL */
     struct DList* dls; /* decision-list pool (ids are 1-based; 0 = none) */
     uint32_t ndl, dl_cap;
+    /* tile pre-cull (term mode): every group and every term has a bit of cull[], the
+     * groups' first (nbound), the terms' after them in collect order, and an entry of
+     * the bound table the block prologue tests against the tile's frustum
+     * (wo_device_common.h tile_culls); the dry run fills tgroups / tterms */
+    int tile_cull;
+    uint32_t nterm, term_bit0;
+    struct TEnt *tgroups, *tterms;
     int err;
 } Gen;
+
+/* an entry of the tile pre-cull's bound table (wodev::TileBound) */
+typedef struct TEnt {
+    int kind; /* 0 never culled, 1 sphere (a = centre, b[0] = R), 2 box (a = low, b = high corner) */
+    float a[3], b[3];
+} TEnt;
 
 /* A BOUND record gets a wave-level test when its subtree has enough leaves and
  * holds more than one primitive: a lone convex primitive's own first member,
@@ -413,8 +426,16 @@ static void gen_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root) {
             static const char* nr[1] = {"bc3"};
             uint32_t nprim = 0;
             for (uint32_t i = 0; i < n; ++i) nprim += p[i].npc ? p[i].npc : 1u;
-            bput(g->b, "%*s{  // group %u (%u primitives)\n%*s  WO_WK(WO_WORK_BOUND_TESTS);\n", indent, "", k, nprim,
-                 indent, "");
+            if (g->tgroups) {
+                TEnt* e = &g->tgroups[k];
+                e->kind = 1;
+                for (int a = 0; a < 3; ++a) e->a[a] = fc[a], e->b[a] = 0.0f;
+                e->b[0] = fR;
+            }
+            /* with the tile pre-cull a bit may be set on entry: the test runs only when it is not */
+            bput(g->b, "%*s{  // group %u (%u primitives)\n", indent, "", k, nprim);
+            if (g->tile_cull) bput(g->b, "%*s  if ((cull[%u] & %uu) == 0u) {\n", indent, "", k / 32, 1u << (k % 32));
+            bput(g->b, "%*s  WO_WK(WO_WORK_BOUND_TESTS);\n", indent, "");
             emit_consts(g->b, indent + 2, "float", nr, &vr2, 1);
             bput(g->b,
                  "%*s  float ox, oy, oz, tca, d2, tr;\n"
@@ -427,6 +448,7 @@ static void gen_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root) {
                  "%*s  if (__ballot(!miss) == 0ull) cull[%u] |= %uu;\n",
                  indent, "", indent, "", fbits(fc[0]), indent, "", fbits(fc[1]), indent, "", fbits(fc[2]), indent, "",
                  indent, "", fbits(fR), indent, "", indent, "", k / 32, 1u << (k % 32));
+            if (g->tile_cull) bput(g->b, "%*s  }\n", indent, "");
             bput(g->b, "%*s}\n%*sif (!(cull[%u] & %uu)) {\n", indent, "", indent, "", k / 32, 1u << (k % 32));
         } else {
             bput(g->b, "%*sif (!(cull[%u] & %uu)) {\n", indent, "", k / 32, 1u << (k % 32));
@@ -526,6 +548,7 @@ static void gen_rtree(Gen* g, int indent);
 static void gen_collect_all(Gen* g, int indent) {
     if (!g->first_pass) gen_cull_barrier(g, indent);
     g->nbound = 0;
+    g->nterm = 0;
     if (g->term_mode)
         gen_collect_terms(g, indent);
     else if (g->rtree)
@@ -672,8 +695,54 @@ static void gen_term_ivl(Gen* g, uint32_t pc, const char* name, int indent) {
     bput(g->b, "%*s  %s = iv;\n%*s}\n", indent, "", name, indent, "");
 }
 
-/* One term: its transitions into best, and at t_min its value into cnt (first pass). */
+static void gen_term_body(Gen* g, const SPrim* q, int indent);
+
+/* A term's entry of the tile pre-cull's table: its sphere (its smallest positive
+ * literal's smallest sphere member, SPrim.r > 0), else the box its positive literals'
+ * axis-aligned half-spaces close (the slab of the slab-minus-crater term), else none. */
+static void term_tile_ent(const Gen* g, const SPrim* q, TEnt* e) {
+    memset(e, 0, sizeof *e);
+    if (q->r > 0.0) {
+        e->kind = 1;
+        for (int a = 0; a < 3; ++a) e->a[a] = (float)q->c[a];
+        e->b[0] = (float)q->r;
+        return;
+    }
+    double lo[3] = {-INFINITY, -INFINITY, -INFINITY}, hi[3] = {INFINITY, INFINITY, INFINITY};
+    for (uint32_t k = 0; k < q->npc; ++k) {
+        if (q->negm & (1u << k)) continue;
+        const uint32_t pc = q->pcs[k];
+        for (uint32_t m = 0; m < g->prog[pc].u0; ++m) {
+            const WoRec* L = &g->prog[pc + 1u + m];
+            if (L->op != WO_LEAF_HALFSPACE || L->u1 < 1u || L->u1 > 3u) continue;
+            const int a = (int)L->u1 - 1; /* s * x_a <= h */
+            if (L->f[a] > 0.0f)
+                hi[a] = fmin(hi[a], (double)L->f[3]);
+            else
+                lo[a] = fmax(lo[a], -(double)L->f[3]);
+        }
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!isfinite(lo[a]) || !isfinite(hi[a]) || lo[a] > hi[a]) return;
+    e->kind = 2;
+    for (int a = 0; a < 3; ++a) e->a[a] = (float)lo[a], e->b[a] = (float)hi[a]; /* fp32 values: exact */
+}
+
+/* One term behind its bit of cull[] (set only by the tile pre-cull). */
 static void gen_term(Gen* g, const SPrim* q, int indent) {
+    if (!g->tile_cull) {
+        gen_term_body(g, q, indent);
+        return;
+    }
+    const uint32_t t = g->nterm++, k = g->term_bit0 + t;
+    if (g->tterms) term_tile_ent(g, q, &g->tterms[t]);
+    bput(g->b, "%*sif (!(cull[%u] & %uu)) {  // tile bit %u\n", indent, "", k / 32, 1u << (k % 32), k);
+    gen_term_body(g, q, indent + 2);
+    bput(g->b, "%*s}\n", indent, "");
+}
+
+/* One term: its transitions into best, and at t_min its value into cnt (first pass). */
+static void gen_term_body(Gen* g, const SPrim* q, int indent) {
     const int first = g->first_pass;
     uint32_t pcs[2] = {q->pcs[0], q->npc > 1u ? q->pcs[1] : 0u};
     int pos[2] = {!(q->negm & 1u), !(q->negm & 2u)};
@@ -2069,6 +2138,8 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
     JTerm* jterms = NULL;
     if (n_prims <= 64u && g.lds_events && n_prims) jterms = jit_terms(prog, n_recs, n_prims, &n_jterms);
     SPrim* tunb = NULL;
+    TEnt *tgroups = NULL, *tterms = NULL;
+    uint32_t n_tile_terms = 0;
     if (jterms) {
         uint32_t* pc_of = (uint32_t*)malloc(sizeof(uint32_t) * n_prims);
         SPrim* units = (SPrim*)calloc(n_jterms, sizeof(SPrim));
@@ -2149,9 +2220,17 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
         Buf* keep = g.b;
         g.b = &scratch;
         g.nbound = 0;
+        g.nterm = 0;
         g.first_pass = 1;
-        gen_collect_terms(&g, 0);
+        g.tile_cull = 1;
+        g.tgroups = tgroups = (TEnt*)calloc(n_jterms + 1u, sizeof(TEnt)); /* a binary hierarchy: fewer groups than units */
+        g.tterms = tterms = (TEnt*)calloc(n_jterms + 1u, sizeof(TEnt));
+        if (!tgroups || !tterms) g.err = 1;
+        if (!g.err) gen_collect_terms(&g, 0);
         nbounds += g.nbound;
+        n_tile_terms = g.nterm;
+        g.term_bit0 = g.nbound;
+        g.tgroups = g.tterms = NULL; /* filled: the emitting passes do not write them */
         g.b = keep;
         free(scratch.s);
     }
@@ -2378,8 +2457,29 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
     for (uint32_t i = 0, o = 0; i < n_recs; ++i)
         if (prog[i].op == WO_OP_PRIM) bput(&b, "%s%uu", o++ ? ", " : "", i);
     bput(&b, "};\n\n");
+    /* the tile pre-cull's table and the tracer's side of the hook (wo_device_common.h
+     * TracerTileCull): an entry per bit of cull[], the groups then the terms */
+    const uint32_t n_tile = g.tile_cull ? nbounds + n_tile_terms : 0u;
+    if (n_tile) {
+        bput(&b, "// tile pre-cull: %u groups + %u terms, one entry per bit of cull[]\n__constant__ wodev::TileBound kTileBound[%u] = {\n",
+             nbounds, n_tile_terms, n_tile);
+        for (uint32_t i = 0; i < n_tile; ++i) {
+            const TEnt* e = i < nbounds ? &tgroups[i] : &tterms[i - nbounds];
+            bput(&b, "  {{%af, %af, %af}, {%af, %af, %af}, %uu},  // bit %u: %s %u, %s\n", (double)e->a[0], (double)e->a[1],
+                 (double)e->a[2], (double)e->b[0], (double)e->b[1], (double)e->b[2], (unsigned)e->kind, i,
+                 i < nbounds ? "group" : "term", i < nbounds ? i : i - nbounds,
+                 e->kind == 1 ? "sphere" : e->kind == 2 ? "box" : "never culled");
+        }
+        bput(&b, "};\n");
+    }
+    bput(&b, "struct JitTracer {\n");
+    if (n_tile)
+        bput(&b,
+             "  static constexpr uint32_t kTileCullEntries = %uu, kTileCullWords = %uu;\n"
+             "  static __device__ __forceinline__ const wodev::TileBound& tile_bound(uint32_t e) { return kTileBound[e]; }\n"
+             "  uint32_t pre[%u];  // the cull words the next trace starts from (pathtrace_block: the tile's, or 0)\n",
+             n_tile, (n_tile + 31u) / 32u, (n_tile + 31u) / 32u);
     bput(&b,
-         "struct JitTracer {\n"
          "  static constexpr bool kCount = WO_COUNT_WORK != 0;  // counting variant: -DWO_COUNT_WORK=1\n"
          "  wodev::WorkCounts wk;\n"
          "  uint64_t tmark;  // end of the first pass (section timing)\n"
@@ -2407,17 +2507,23 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
         bput(&b, "    return false;\n  }\n};\n");
     } else {
         bput(&b, "    const float tmin = WO_T_MIN;\n");
+        if (n_tile) { /* a tile none of whose rays can meet anything: no hit, before any arithmetic */
+            bput(&b, "    if (");
+            for (uint32_t w = 0; w < (n_tile + 31u) / 32u; ++w)
+                bput(&b, "%s(pre[%u] == 0x%08xu)", w ? " & " : "", w, n_tile - 32u * w >= 32u ? 0xffffffffu : (1u << (n_tile - 32u * w)) - 1u);
+            bput(&b, ") return false;\n");
+        }
         /* reciprocal direction components for the axes axis-aligned half-spaces use */
         uint32_t axes = 0;
         for (uint32_t i = 0; i < n_recs; ++i)
             if (prog[i].op == WO_LEAF_HALFSPACE && prog[i].u1 >= 1u && prog[i].u1 <= 3u) axes |= 1u << (prog[i].u1 - 1u);
         for (int a = 0; a < 3; ++a)
             if (axes & (1u << a)) bput(&b, "    const float iv%c = wodev::rcp_dir(d.%c);\n", "xyz"[a], "xyz"[a]);
-        uint32_t ncw = nbounds ? (nbounds + 31u) / 32u : 1u;
+        uint32_t ncw = nbounds + n_tile_terms ? (nbounds + n_tile_terms + 31u) / 32u : 1u;
         g.ncw = ncw;
         if (g.term_mode) {
-            bput(&b, "    uint32_t cull[%u];  // bit k: group k culled for this wave\n", ncw);
-            for (uint32_t w = 0; w < ncw; ++w) bput(&b, "    cull[%u] = 0u;\n", w);
+            bput(&b, "    uint32_t cull[%u];  // bit k: group k culled for this wave; the terms' bits after the groups'\n", ncw);
+            for (uint32_t w = 0; w < ncw; ++w) bput(&b, "    cull[%u] = pre[%u];\n", w, w);
             bput(&b,
                  "    // the smallest term transition after `after` (its rise flag in the key)\n"
                  "    // and the number of terms true at t_min\n"
@@ -2763,6 +2869,7 @@ kernel_tail:
          "    const WoRec* __restrict__ prog, const WoMaterial* __restrict__ mats, WoFrame fr, uint32_t local_rows,\n"
          "    float4* __restrict__ out, unsigned long long* __restrict__ seg_slots, wodev::PathLaunch tg) {\n"
          "  JitTracer tr;\n"
+         "%s"
          "#if WO_JIT_LDS_EVENTS\n"
          "  __shared__ uint64_t s_ev[wodev::kLdsEvents * wodev::kBlock];\n"
          "  tr.ev = s_ev + threadIdx.x;\n"
@@ -2804,6 +2911,7 @@ kernel_tail:
          "#endif\n"
          "  wodev::pathtrace_block(tr, m, fr, local_rows, out, seg_slots, tg);\n"
          "}\n",
+         n_tile ? "  for (uint32_t w = 0; w < JitTracer::kTileCullWords; ++w) tr.pre[w] = 0u;\n" : "",
          n_recs ? n_recs : 1u, n_mats_used, n_prims ? n_prims : 1u, n_recs * 8u, n_mats_used * 8u, n_prims);
     /* the root evaluation's operation count per swept event, for bench.py's
      * executed-work roofline (0: not known, e.g. the postfix form) */
@@ -2819,6 +2927,8 @@ kernel_tail:
     free(uterms);
     free(sprims);
     free(tunb);
+    free(tgroups);
+    free(tterms);
     free(jterms);
     if (g.err || b.oom) {
         free(b.s);
