@@ -37,6 +37,9 @@ static const AbiField kAbi[] = {
     F(WoFrame, mode), F(WoFrame, sample_offset), F(WoFrame, tile_rows), F(WoFrame, rank), F(WoFrame, nranks),
     F(WoFrame, n_recs), F(WoFrame, n_prims), F(WoFrame, time_sec), F(WoFrame, sphere_y), F(WoFrame, inv_width),
     F(WoFrame, inv_height), F(WoFrame, cam), F(WoFrame, band_cycle), F(WoFrame, band_skip),
+    T(Wo_Ray), F(Wo_Ray, origin), F(Wo_Ray, t_max), F(Wo_Ray, dir), F(Wo_Ray, reserved),
+    T(Wo_RayHit), F(Wo_RayHit, t), F(Wo_RayHit, flags), F(Wo_RayHit, leaf), F(Wo_RayHit, node),
+    F(Wo_RayHit, normal), F(Wo_RayHit, material),
 };
 
 #undef T

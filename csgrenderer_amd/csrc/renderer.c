@@ -273,6 +273,7 @@ void wo_renderer_del(Wo_Renderer* r) {
     free(r->nonroot);
     free(r->mats);
     free(r->prog);
+    free(r->prog_nodes);
     free(r->name);
     free(r);
 }
@@ -446,6 +447,12 @@ WoRec const* wo_renderer_program(Wo_Renderer* r, uint32_t* n_recs, uint32_t* n_p
     return r->prog;
 }
 
+Wo_Node const* wo_renderer_program_nodes(Wo_Renderer* r, uint32_t* n_recs) {
+    if (!r || wo_renderer_compile(r) < 0) return NULL;
+    if (n_recs) *n_recs = r->n_recs;
+    return r->prog_nodes;
+}
+
 WoMaterial const* wo_renderer_materials(Wo_Renderer* r, uint32_t* n_materials) {
     if (n_materials) *n_materials = r->n_mats;
     return r->mats;
@@ -579,6 +586,12 @@ static int sync_device_ex(Wo_Renderer* r, int may_defer) {
                 return -1;
             }
         }
+        /* the records' source nodes, for ray queries (d0 only: wo_renderer_trace_rays_device) */
+        if (wo_dev_upload_nodes(r->dev, r->prog_nodes, r->n_recs, err, sizeof err)) {
+            wo_set_error("scene upload failed (node table): %s", err);
+            if (cur >= 0) (void)wo_dev_select(cur);
+            return -1;
+        }
         r->dev_stale = 0;
         r->jit_loaded = 0;
         r->lanes_loaded = 0;
@@ -696,7 +709,9 @@ int wo_renderer_jit_info(Wo_Renderer* r, double* seconds) {
 }
 
 int wo_renderer_lanes_info(Wo_Renderer* r, uint32_t* out) {
-    if (!r || !r->dev || !r->lanes_loaded || !out) return -1;
+    if (!r || !r->dev || !out) return -1;
+    /* the path kernel is the lane tracer, or the last ray query ran on it */
+    if (!r->lanes_loaded && wo_dev_ray_form(r->dev) != 2) return -1;
     return wo_dev_lanes_info(r->dev, out);
 }
 
@@ -750,6 +765,91 @@ int wo_renderer_count_work(Wo_Renderer* r, Wo_RenderParams const* params, uint32
         return -1;
     }
     return 0;
+}
+
+/* ---------------------------------------------------------------- ray queries */
+
+/* the kernels read a ray and write a hit as two 16-byte rows each */
+_Static_assert(sizeof(Wo_Ray) == 32 && sizeof(Wo_RayHit) == 32, "Wo_Ray / Wo_RayHit are 32 bytes");
+_Static_assert(offsetof(Wo_Ray, dir) == 16 && offsetof(Wo_RayHit, normal) == 16, "second 16-byte row");
+
+void wo_renderer_set_ray_tracer(Wo_Renderer* r, Wo_RayTracer tracer) {
+    if (r) r->ray_tracer = (int)tracer;
+}
+
+char const* wo_renderer_ray_path(Wo_Renderer* r) {
+    const int form = r && r->dev ? wo_dev_ray_form(r->dev) : 0;
+    return form == 2 ? "lanes" : form == 1 ? "interpreter" : "none";
+}
+
+int wo_renderer_trace_rays_device(Wo_Renderer* r, Wo_Ray const* d_rays, Wo_RayHit* d_hits, size_t n, void* stream) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    if (n == 0) return 0;
+    if (!d_rays || !d_hits) {
+        wo_set_error("trace_rays: NULL ray or hit buffer");
+        return -1;
+    }
+    char err[256] = {0};
+    if (wo_dev_trace_rays(r->dev, d_rays, d_hits, n, r->ray_tracer, stream, err, sizeof err)) {
+        wo_set_error("ray launch failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_trace_rays(Wo_Renderer* r, Wo_Ray const* rays, Wo_RayHit* hits, size_t n) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    if (n == 0) return 0;
+    if (!rays || !hits) {
+        wo_set_error("trace_rays: NULL ray or hit buffer");
+        return -1;
+    }
+    char err[256] = {0};
+    if (wo_dev_trace_rays_host(r->dev, rays, hits, n, r->ray_tracer, err, sizeof err)) {
+        wo_set_error("ray query failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+/* oracle.c normalize3 / sqrt_pt, one rounding per operation (-ffp-contract=off) */
+static void normalize3f(float v[3]) {
+    const float dot = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    const float inv = 1.0f / sqrtf(fmaxf(dot, 0x1p-96f));
+    v[0] = v[0] * inv;
+    v[1] = v[1] * inv;
+    v[2] = v[2] * inv;
+}
+
+int wo_renderer_pixel_ray(Wo_Renderer* r, Wo_RenderParams const* p, uint32_t x, uint32_t y, Wo_Ray* out) {
+    if (!r || !p || !out) return -1;
+    if (x >= p->width || y >= p->height) {
+        wo_set_error("pixel (%u, %u) outside the %ux%u frame", x, y, p->width, p->height);
+        return -1;
+    }
+    /* the WO_SHADING_NORMALS sample of oracle.c shade_pixel: the pixel centre, no lens offset */
+    WoCamera cam;
+    wo_resolve_camera(&r->camera, p->width, p->height, &cam);
+    const float inv_width = 1.0f / (float)p->width, inv_height = 1.0f / (float)p->height;
+    const float u = ((float)x + 0.5f) * inv_width;
+    const float v = ((float)(p->height - 1u - y) + 0.5f) * inv_height;
+    const float off = 0.0f;
+    for (int i = 0; i < 3; ++i) {
+        out->origin[i] = cam.origin[i] + off;
+        out->dir[i] = ((cam.lower_left[i] + u * cam.horizontal[i]) + v * cam.vertical[i]) - cam.origin[i] - off;
+    }
+    normalize3f(out->dir);
+    out->t_max = INFINITY;
+    out->reserved = 0u;
+    return 0;
+}
+
+int wo_renderer_pick(Wo_Renderer* r, Wo_RenderParams const* params, uint32_t x, uint32_t y, Wo_RayHit* out) {
+    Wo_Ray ray;
+    if (!out || wo_renderer_pixel_ray(r, params, x, y, &ray)) return -1;
+    return wo_renderer_trace_rays(r, &ray, out, 1);
 }
 
 int wo_assemble_rows_device_ex(void const* d_gathered, void* d_frame, uint32_t width, uint32_t height,

@@ -38,6 +38,7 @@ typedef struct ENode {
     double c[3], rad;   /* sphere */
     double n[3], h;     /* half-space {x : n.x <= h} */
     uint32_t material;
+    Wo_Node src;        /* leaves: the node this instance was expanded from */
     /* analysis */
     int convex;
     int need;
@@ -56,6 +57,7 @@ typedef struct Ctx {
     ENode* e;
     size_t n, cap;
     WoRec* prog;
+    Wo_Node* nodes;     /* per record: the leaf's source node, else WO_NODE_INVALID (grows with prog) */
     uint32_t n_recs, cap_recs;
     uint32_t ordinal;
     char* err;
@@ -162,6 +164,7 @@ static int expand(Ctx* c, Wo_Node node, const Xf* xf, int depth) {
     case WO_NODE_SPHERE: {
         ENode* e = &c->e[id];
         e->kind = E_SPHERE;
+        e->src = node;
         for (int i = 0; i < 3; ++i) e->c[i] = xf->t[i];
         e->rad = fabs(ni->radius);
         e->material = ni->material < r->n_mats ? ni->material : 0u;
@@ -172,6 +175,7 @@ static int expand(Ctx* c, Wo_Node node, const Xf* xf, int depth) {
         double n[3] = {ni->normal.x, ni->normal.y, ni->normal.z};
         double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
         e->kind = E_HALF;
+        e->src = node;
         if (len > 0.0 && isfinite(len)) {
             for (int i = 0; i < 3; ++i) n[i] /= len;
             quat_rotate(xf->q, n, e->n);
@@ -659,8 +663,15 @@ static WoRec* push_rec(Ctx* c) {
             return NULL;
         }
         c->prog = np;
+        Wo_Node* nn = (Wo_Node*)realloc(c->nodes, nc * sizeof(Wo_Node));
+        if (!nn) {
+            fail(c, "out of host memory");
+            return NULL;
+        }
+        c->nodes = nn;
         c->cap_recs = nc;
     }
+    c->nodes[c->n_recs] = WO_NODE_INVALID;
     WoRec* rec = &c->prog[c->n_recs++];
     memset(rec, 0, sizeof *rec);
     return rec;
@@ -675,6 +686,7 @@ static float round_up_f(double v) {
 static void emit_leaf(Ctx* c, const ENode* m) {
     WoRec* rec = push_rec(c);
     if (!rec) return;
+    c->nodes[c->n_recs - 1u] = m->src; /* wo_renderer_program_nodes: every instance names its node */
     rec->u0 = m->material;
     if (m->kind == E_SPHERE) {
         /* every fp32 value of the record finite: the kernels' square root of the
@@ -824,18 +836,24 @@ int wo_compile_scene(Wo_Renderer* r, char* err, size_t errlen) {
     free(c.e);
     if (c.failed) {
         free(c.prog);
+        free(c.nodes);
         return -1;
     }
     if (!c.prog) { /* empty scene: keep a valid (zero-record) program pointer */
         c.prog = (WoRec*)calloc(1, sizeof(WoRec));
+        c.nodes = (Wo_Node*)calloc(1, sizeof(Wo_Node));
         c.cap_recs = 1;
-        if (!c.prog) {
+        if (!c.prog || !c.nodes) {
+            free(c.prog);
+            free(c.nodes);
             snprintf(err, errlen, "out of host memory");
             return -1;
         }
     }
     free(r->prog);
+    free(r->prog_nodes);
     r->prog = c.prog;
+    r->prog_nodes = c.nodes;
     r->n_recs = c.n_recs;
     r->cap_recs = c.cap_recs;
     r->n_prims = c.ordinal;

@@ -1237,6 +1237,172 @@ __global__ __launch_bounds__(kBlock) void pathtrace_kernel(const WoRec* __restri
     pathtrace_block(tr, mats, fr, local_rows, out, seg_slots, tg);
 }
 
+// ---------------------------------------------------------------------------
+// Ray queries (wo_renderer_trace_rays_device): the tracers above on the caller's
+// rays instead of camera jobs.  A ray is two float4 (origin | t_max, dir |
+// reserved: Wo_Ray), a hit two float4 (t, flags, leaf, node | normal, material:
+// Wo_RayHit); one ray per lane, grid-stride over a grid of resident workgroups,
+// so the workgroup's prologue (program / top BVH nodes into LDS) is paid once
+// for many rays.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kRayHit = 1u, kRayExit = 2u, kRayEnters = 4u, kRayInvalid = 8u;  // WO_RAY_* (renderer_ext.h)
+
+struct RayBatch {
+    const float4* __restrict__ rays;
+    float4* __restrict__ hits;
+    const uint32_t* __restrict__ nodes;  // per program record: its source node handle
+    uint64_t n;
+    uint32_t n_mats;
+};
+
+// Finite origin and direction, a direction that is not zero, t_max not NaN
+// (t_max = -inf is a valid ray that no hit satisfies).
+__device__ __forceinline__ bool ray_valid(const float4& r0, const float4& r1) {
+    const bool fin = (fabsf(r0.x) < kInf) & (fabsf(r0.y) < kInf) & (fabsf(r0.z) < kInf) & (fabsf(r1.x) < kInf) &
+                     (fabsf(r1.y) < kInf) & (fabsf(r1.z) < kInf);
+    const bool nonzero = (r1.x != 0.0f) | (r1.y != 0.0f) | (r1.z != 0.0f);
+    return fin & nonzero & !(r0.w != r0.w);
+}
+
+// Ray i's result: a hit (`found`: the root flips at h.t <= t_max; `leaf` = the hit
+// member's record) with the solid's outward normal as the path tracer's NORMALS
+// shading forms it (oracle.c shade_pixel), or the miss encoding.
+__device__ __forceinline__ void ray_store(const RayBatch& rb, const WoRec* __restrict__ prog, uint64_t i, bool valid,
+                                          bool found, const Hit& h, uint32_t leaf, F3 o, F3 d) {
+    float4 h0 = make_float4(kInf, __uint_as_float(valid ? 0u : kRayInvalid), __uint_as_float(0xffffffffu),
+                            __uint_as_float(0xffffffffu));
+    float4 h1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu));
+    if (found) {
+        const WoRec L = prog[leaf];
+        const F3 P = f3(o.x + h.t * d.x, o.y + h.t * d.y, o.z + h.t * d.z);
+        F3 n;
+        if (L.op == WO_LEAF_SPHERE)
+            n = f3((P.x - L.f[0]) * L.f[4], (P.y - L.f[1]) * L.f[4], (P.z - L.f[2]) * L.f[4]);
+        else
+            n = f3(L.f[0], L.f[1], L.f[2]);
+        const F3 N = h.type() == 0u ? n : f3(-n.x, -n.y, -n.z);
+        const F3 ns = h.root_after != 0u ? N : f3(-N.x, -N.y, -N.z);
+        const uint32_t flags = kRayHit | (h.type() ? kRayExit : 0u) | (h.root_after ? kRayEnters : 0u);
+        h0 = make_float4(h.t, __uint_as_float(flags), __uint_as_float(leaf), __uint_as_float(rb.nodes[leaf]));
+        h1 = make_float4(ns.x, ns.y, ns.z, __uint_as_float(L.u0 < rb.n_mats ? L.u0 : 0u));
+    }
+    rb.hits[2u * i] = h0;
+    rb.hits[2u * i + 1u] = h1;
+}
+
+// The interpreter over rays (any scene).  Its walk is wave-uniform, so every lane
+// of a tracing wave needs a ray: lanes past n and lanes with an invalid ray trace
+// a copy of the wave's first valid ray and drop the result (a copy adds no BOUND
+// the wave would not enter anyway, and a lane's events are its own: a ray's result
+// does not depend on its wave-mates); a wave without a valid ray skips the trace.
+// The hit's ordinal counts the primitives the wave kept; its record index comes
+// from the wave's own ordinal -> pc map.
+template <bool kProgInLds>
+__global__ __launch_bounds__(kBlock) void trace_rays_kernel(const WoRec* __restrict__ gprog, uint32_t nrec,
+                                                            KLayout lay, RayBatch rb) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uni(tid >> 6);
+
+    uint32_t* scratch = smem;
+    InterpTracer<false> tr;
+    if constexpr (kProgInLds) {
+        const uint4* src = reinterpret_cast<const uint4*>(gprog);
+        uint4* dst = reinterpret_cast<uint4*>(smem);
+        for (uint32_t i = tid; i < nrec * 2u; i += kBlock) dst[i] = src[i];
+        __syncthreads();
+        tr.prog.p = reinterpret_cast<const WoRec*>(smem);
+        scratch = smem + nrec * 8u;
+    } else {
+        tr.prog.p = gprog;
+    }
+    uint32_t* ws = scratch + wave * lay.wave_words;
+    tr.nrec = nrec;
+    tr.codes = ws;
+    tr.ordpc = ws + lay.ordpc_off;
+    tr.hib = ws + lay.hib_off;
+    tr.lane = lane;
+
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t base = (uint64_t)blockIdx.x * kBlock + wave * 64u; base < rb.n; base += stride) {
+        const uint64_t i = base + lane;
+        const bool in = i < rb.n;
+        float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+        if (in) {
+            r0 = rb.rays[2u * i];
+            r1 = rb.rays[2u * i + 1u];
+        }
+        const bool valid = in && ray_valid(r0, r1);
+        const uint64_t vm = __ballot(valid);
+        const F3 o = f3(r0.x, r0.y, r0.z), d = f3(r1.x, r1.y, r1.z);
+        bool found = false;
+        uint32_t leaf = 0;
+        Hit h;
+        h.t = kInf;
+        h.lo = 0;
+        h.root_after = 0;
+        if (vm != 0ull) {
+            const int src = __builtin_ctzll(vm);
+            auto from = [&](float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), src)); };
+            const F3 so = f3(from(o.x), from(o.y), from(o.z)), sd = f3(from(d.x), from(d.y), from(d.z));
+            const F3 to = valid ? o : so, td = valid ? d : sd;
+            found = tr.trace(to, td, h);
+            found = found & valid & (h.t <= r0.w);
+            if (found) leaf = tr.ordpc[h.ord()] + 1u + h.member();
+        }
+        if (in) ray_store(rb, gprog, i, valid, found, h, leaf, o, d);
+    }
+}
+
+// The lane tracer's ordered BVH walk over rays (union-only scenes; forms 2 and 3 of
+// pathtrace_lanes_kernel, the plain trace).  Every lane walks on its own, so a lane
+// without a valid ray simply does not trace.
+template <int kMode>
+__global__ __launch_bounds__(kBlock, kMode == 2 ? WO_LANES_BVH_MIN_WAVES : WO_LANES_MIN_WAVES) void trace_rays_lanes_kernel(
+    const WoRec* __restrict__ prog, const uint32_t* __restrict__ ordpc, LaneBvh bvh, RayBatch rb) {
+    static_assert(kMode == 2 || kMode == 3, "ray queries walk the union-only forms");
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    LaneTracer<kMode, false> tr;
+    tr.prog = prog;
+    tr.ordpc = ordpc;
+    tr.lnodes = bvh.nodes;
+    tr.lgeo = bvh.geo;
+    tr.lkind = bvh.kind;
+    tr.ltrec = bvh.trec;
+    tr.lleaf = bvh.leaves;
+    tr.nalways = bvh.nalways;
+    tr.lroot = bvh.root;
+    tr.nprims = bvh.nprims;
+    tr.stk = smem + threadIdx.x;
+    tr.stk16 = reinterpret_cast<uint16_t*>(smem) + threadIdx.x;
+    {
+        // the top levels of the BVH next to the stacks, as pathtrace_lanes_kernel lays them out
+        float4* top = reinterpret_cast<float4*>(smem + ((bvh.depth * kBlock + 3u) & ~3u));
+        for (uint32_t i = threadIdx.x; i < 4u * bvh.ntop; i += kBlock) top[i] = bvh.nodes[i];
+        tr.ltop = (typename LaneTracer<kMode, false>::LdsNodes)top;
+        tr.ntop = bvh.ntop;
+    }
+    __syncthreads();
+
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < rb.n; i += stride) {
+        const float4 r0 = rb.rays[2u * i], r1 = rb.rays[2u * i + 1u];
+        const bool valid = ray_valid(r0, r1);
+        const F3 o = f3(r0.x, r0.y, r0.z), d = f3(r1.x, r1.y, r1.z);
+        bool found = false;
+        uint32_t leaf = 0;
+        Hit h;
+        h.t = kInf;
+        h.lo = 0;
+        h.root_after = 0;
+        if (valid) {
+            found = tr.trace(o, d, h);
+            found = found & (h.t <= r0.w);
+            if (found) leaf = ordpc[h.ord()] + 1u + h.member();
+        }
+        ray_store(rb, prog, i, valid, found, h, leaf, o, d);
+    }
+}
+
 // Sums (and clears) the segment slots into the caller's counter.
 __global__ __launch_bounds__(kBlock) void seg_collect_kernel(unsigned long long* __restrict__ slots,
                                                              unsigned long long* __restrict__ counter) {
@@ -1426,6 +1592,15 @@ struct WoDev {
     uint32_t lb_gclip_off;               // u32 offset of the primitives' relevance boxes (0: none)
     uint32_t lb_gP, lb_gwords, lb_groot;  // leaves (= primitives), bit words per lane, the root's ref
     uint32_t last_kind;    // the PathKind of the last path launch (wo_dev_lanes_info)
+    // ray queries (wo_dev_trace_rays): per program record its source node handle, the
+    // host form's staging buffer (rays, then hits), and the last ray launch's kernel
+    uint32_t* d_nodes;
+    size_t nodes_cap;
+    uint32_t n_nodes;
+    float4* d_rayio;
+    size_t rayio_cap;
+    uint32_t ray_kind;     // its PathKind (kLanesBvh / kLanesBvhSpheres / kInterpLds / kInterpGlobal; 0: none yet)
+    bool ray_last;         // the last path or ray launch was a ray launch (wo_dev_lanes_info's form)
     uint32_t lb_term_off;  // their records (kTermRecF4 float4 each) at this u32 offset of d_lbvh
     uint32_t lb_leaf_off;  // single-sphere scenes: per ordinal its leaf record (WoRec) at this u32 offset, else 0
     uint32_t lb_top;       // nodes staged in LDS per workgroup
@@ -1579,6 +1754,8 @@ extern "C" void wo_dev_destroy(WoDev* dev) {
     if (dev->d_frame) (void)hipFree(dev->d_frame);
     if (dev->d_lbvh) (void)hipFree(dev->d_lbvh);
     if (dev->d_ordpc) (void)hipFree(dev->d_ordpc);
+    if (dev->d_nodes) (void)hipFree(dev->d_nodes);
+    if (dev->d_rayio) (void)hipFree(dev->d_rayio);
     if (dev->d_segslots) (void)hipFree(dev->d_segslots);
     if (dev->d_work) (void)hipFree(dev->d_work);
     if (dev->d_accum) (void)hipFree(dev->d_accum);
@@ -2455,6 +2632,7 @@ extern "C" int wo_dev_upload_scene(WoDev* dev, WoRec const* prog, uint32_t n_rec
     dev->n_recs = n_recs;
     dev->n_prims = n_prims;
     dev->n_mats = n_mats;
+    dev->n_nodes = ~0u;  // the node table is the previous scene's until wo_dev_upload_nodes
     if (scene_maps(dev, prog, n_recs, n_prims, err, errlen)) return -1;
     return build_lbvh(dev, prog, n_recs, n_prims, mats, n_mats, err, errlen);
 }
@@ -2917,7 +3095,7 @@ extern "C" int wo_dev_lanes_info(WoDev* dev, uint32_t* out) {
     out[1] = dev->lb_depth;
     out[2] = dev->lb_top;
     out[3] = dev->lb_always;
-    out[4] = dev->last_kind;
+    out[4] = dev->ray_last ? dev->ray_kind : dev->last_kind;
     return 0;
 }
 
@@ -3140,6 +3318,32 @@ static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* s
                        unsigned long long* d_segments, long long* d_accum, uint32_t accum_spp, bool count, char* err,
                        size_t errlen);
 
+// The interpreter's per-wave LDS scratch (KLayout) for a program of n_recs records
+// and n_prims primitives, and its form: the program in LDS too when both fit
+// (kInterpLds), else read from global memory (kInterpGlobal).  The frame kernel
+// and the ray kernel share it.
+static int interp_plan(uint32_t n_recs, uint32_t n_prims, KLayout* lay, PathKind* kind, size_t* dyn_lds, char* err,
+                       size_t errlen) {
+    lay->codes_words = (n_recs + 7u) / 8u + 1u;
+    lay->ordpc_off = lay->codes_words;
+    uint32_t hib_words = n_prims > 64u ? (n_prims - 64u + 31u) / 32u : 0u;
+    lay->hib_off = lay->ordpc_off + n_prims;
+    lay->wave_words = (lay->hib_off + hib_words * 64u + 3u) & ~3u;
+    size_t scratch = (size_t)(kBlock / 64u) * lay->wave_words * 4u;
+    size_t prog_bytes = (size_t)n_recs * sizeof(WoRec);
+    if (prog_bytes + scratch <= kLdsBudget) {
+        *kind = kInterpLds;
+        *dyn_lds = prog_bytes + scratch;
+    } else if (scratch <= kLdsBudget) {
+        *kind = kInterpGlobal;
+        *dyn_lds = scratch;
+    } else {
+        snprintf(err, errlen, "scene too large for the LDS scratch (%zu bytes per workgroup)", scratch);
+        return -1;
+    }
+    return 0;
+}
+
 extern "C" int wo_dev_launch_ex(WoDev* dev, WoFrame const* frame_in, void* d_out, void* stream_v,
                                 unsigned long long* d_segments, long long* d_accum, uint32_t accum_spp, char* err,
                                 size_t errlen) {
@@ -3213,26 +3417,11 @@ static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* s
             if (dev->lb_general) dyn_lds += (size_t)dev->lb_gwords * kBlock * sizeof(uint32_t);  // the tree's bits
         } else if (dev->jit_fn) {
             kind = kJit;
-        } else {
-            lay.codes_words = (fr.n_recs + 7u) / 8u + 1u;
-            lay.ordpc_off = lay.codes_words;
-            uint32_t hib_words = fr.n_prims > 64u ? (fr.n_prims - 64u + 31u) / 32u : 0u;
-            lay.hib_off = lay.ordpc_off + fr.n_prims;
-            lay.wave_words = (lay.hib_off + hib_words * 64u + 3u) & ~3u;
-            size_t scratch = (size_t)(kBlock / 64u) * lay.wave_words * 4u;
-            size_t prog_bytes = (size_t)fr.n_recs * sizeof(WoRec);
-            if (prog_bytes + scratch <= kLdsBudget) {
-                kind = kInterpLds;
-                dyn_lds = prog_bytes + scratch;
-            } else if (scratch <= kLdsBudget) {
-                kind = kInterpGlobal;
-                dyn_lds = scratch;
-            } else {
-                snprintf(err, errlen, "scene too large for the LDS scratch (%zu bytes per workgroup)", scratch);
-                return -1;
-            }
+        } else if (interp_plan(fr.n_recs, fr.n_prims, &lay, &kind, &dyn_lds, err, errlen)) {
+            return -1;
         }
         dev->last_kind = (uint32_t)kind;
+        dev->ray_last = false;
         int per_cu = 0;
         hipFunction_t jfn = count ? dev->count_fn : dev->jit_fn;
         if (kind == kJit)
@@ -3283,6 +3472,143 @@ static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* s
     e = hipGetLastError();
     if (e != hipSuccess) {
         set_err(err, errlen, "kernel launch", e);
+        return -1;
+    }
+    return 0;
+}
+
+// ---- ray queries ----
+
+extern "C" int wo_dev_upload_nodes(WoDev* dev, uint32_t const* nodes, uint32_t n_recs, char* err, size_t errlen) {
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    dev->n_nodes = ~0u;
+    if (ensure_buffer(&dev->d_nodes, &dev->nodes_cap, (size_t)n_recs * sizeof(uint32_t), err, errlen)) return -1;
+    if (n_recs) {
+        e = hipMemcpy(dev->d_nodes, nodes, (size_t)n_recs * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            set_err(err, errlen, "hipMemcpy(node table)", e);
+            return -1;
+        }
+    }
+    dev->n_nodes = n_recs;
+    return 0;
+}
+
+extern "C" int wo_dev_ray_form(WoDev* dev) {
+    if (!dev || dev->ray_kind == 0u) return 0;
+    return dev->ray_kind == kLanesBvh || dev->ray_kind == kLanesBvhSpheres ? 2 : 1;
+}
+
+// Workgroups of a ray launch: one ray per lane, at most the workgroups the device
+// holds at once (the grid-stride loop takes the rest).  WOLOLO_RAY_BLOCKS
+// (measurement) caps the grid.
+static uint32_t ray_grid(const WoDev* dev, size_t n, int per_cu) {
+    uint64_t blocks = ((uint64_t)n + kBlock - 1u) / kBlock;
+    uint64_t resident = (uint64_t)dev->cus * (uint64_t)(per_cu < 1 ? 1 : per_cu);
+    const char* cap = getenv("WOLOLO_RAY_BLOCKS");
+    if (cap && *cap && atoi(cap) > 0) resident = (uint64_t)atoi(cap);
+    return (uint32_t)(blocks < resident ? blocks : resident);
+}
+
+extern "C" int wo_dev_trace_rays(WoDev* dev, void const* d_rays, void* d_hits, size_t n, int form, void* stream_v,
+                                 char* err, size_t errlen) {
+    hipStream_t stream = (hipStream_t)stream_v;  // NULL = the null stream (HIP convention)
+    if (n == 0) return 0;
+    if (!dev->d_prog || !dev->d_nodes || dev->n_nodes != dev->n_recs) {
+        snprintf(err, errlen, "no scene (or no node table) on the device");
+        return -1;
+    }
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) {
+        snprintf(err, errlen, "ray and hit buffers must be 16-byte aligned");
+        return -1;
+    }
+    if (dev->n_prims >= (1u << 20)) {
+        snprintf(err, errlen, "scene has %u primitives (max %u)", dev->n_prims, (1u << 20) - 1u);
+        return -1;
+    }
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    RayBatch rb;
+    rb.rays = (const float4*)d_rays;
+    rb.hits = (float4*)d_hits;
+    rb.nodes = dev->d_nodes;
+    rb.n = n;
+    rb.n_mats = dev->n_mats;
+    // the lane walk for a union-only scene (its BVH is built at every upload), unless
+    // the interpreter is asked for; a scene that is not union-only has no plain walk
+    const bool lanes = form != 1 && dev->union_only && !dev->lb_terms && !dev->lb_general && !dev->lb_wide;
+    PathKind kind;
+    size_t dyn_lds = 0;
+    KLayout lay = {};
+    int per_cu = 0;
+    if (lanes) {
+        kind = dev->lb_spheres_only ? kLanesBvhSpheres : kLanesBvh;
+        const size_t stacks = ((size_t)dev->lb_depth * kBlock * 4u + 15u) & ~(size_t)15u;
+        dyn_lds = stacks + (size_t)dev->lb_top * 4u * sizeof(float4);
+        e = kind == kLanesBvh
+                ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_lanes_kernel<2>, kBlock, dyn_lds)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_lanes_kernel<3>, kBlock, dyn_lds);
+        if (e != hipSuccess || per_cu < 1) per_cu = 1;
+        const dim3 grid(ray_grid(dev, n, per_cu));
+        if (kind == kLanesBvh)
+            hipLaunchKernelGGL(trace_rays_lanes_kernel<2>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->d_ordpc,
+                               lane_bvh(dev), rb);
+        else
+            hipLaunchKernelGGL(trace_rays_lanes_kernel<3>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->d_ordpc,
+                               lane_bvh(dev), rb);
+    } else {
+        if (interp_plan(dev->n_recs, dev->n_prims, &lay, &kind, &dyn_lds, err, errlen)) return -1;
+        e = kind == kInterpLds
+                ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_kernel<true>, kBlock, dyn_lds)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_kernel<false>, kBlock, dyn_lds);
+        if (e != hipSuccess || per_cu < 1) per_cu = 1;
+        const dim3 grid(ray_grid(dev, n, per_cu));
+        if (kind == kInterpLds)
+            hipLaunchKernelGGL(trace_rays_kernel<true>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->n_recs, lay,
+                               rb);
+        else
+            hipLaunchKernelGGL(trace_rays_kernel<false>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->n_recs,
+                               lay, rb);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err(err, errlen, "ray kernel launch", e);
+        return -1;
+    }
+    dev->ray_kind = (uint32_t)kind;
+    dev->ray_last = true;
+    return 0;
+}
+
+extern "C" int wo_dev_trace_rays_host(WoDev* dev, void const* rays, void* hits, size_t n, int form, char* err,
+                                      size_t errlen) {
+    if (n == 0) return 0;
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    const size_t bytes = n * 2u * sizeof(float4);  // rays, and as many bytes of hits behind them
+    if (ensure_buffer(&dev->d_rayio, &dev->rayio_cap, 2u * bytes, err, errlen)) return -1;
+    float4* d_rays = dev->d_rayio;
+    float4* d_hits = dev->d_rayio + 2u * n;
+    e = hipMemcpyAsync(d_rays, rays, bytes, hipMemcpyHostToDevice, dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipMemcpy(rays)", e);
+        return -1;
+    }
+    if (wo_dev_trace_rays(dev, d_rays, d_hits, n, form, dev->stream, err, errlen)) return -1;
+    e = hipMemcpyAsync(hits, d_hits, bytes, hipMemcpyDeviceToHost, dev->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "ray query", e);
         return -1;
     }
     return 0;

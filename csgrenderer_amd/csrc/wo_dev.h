@@ -73,6 +73,21 @@ int wo_dev_launch(WoDev* dev, WoFrame const* frame, void* d_out, void* stream,
 int wo_dev_launch_ex(WoDev* dev, WoFrame const* frame, void* d_out, void* stream,
                      unsigned long long* d_segments, long long* d_accum, uint32_t accum_spp, char* err,
                      size_t errlen);
+/* Ray queries (renderer_ext.h wo_renderer_trace_rays_device): n Wo_Ray at d_rays
+ * -> n Wo_RayHit at d_hits (device memory, 32 bytes each, 16-byte aligned), async on
+ * `stream`.  `form` is a Wo_RayTracer: 0 the lane walk for a union-only scene, else
+ * the interpreter; 1 the interpreter; 2 the lane walk where it applies (else the
+ * interpreter).  The specialised kernel is never used. */
+int wo_dev_trace_rays(WoDev* dev, void const* d_rays, void* d_hits, size_t n, int form, void* stream, char* err,
+                      size_t errlen);
+/* The same from and to host memory, through the device's own buffer and stream
+ * (synchronous). */
+int wo_dev_trace_rays_host(WoDev* dev, void const* rays, void* hits, size_t n, int form, char* err, size_t errlen);
+/* Per program record its source node handle (Wo_Renderer::prog_nodes), read by the
+ * ray kernels; uploaded with the scene (blocking, after wo_dev_upload_scene). */
+int wo_dev_upload_nodes(WoDev* dev, uint32_t const* nodes, uint32_t n_recs, char* err, size_t errlen);
+/* Kernel of the last ray launch: 0 none, 1 the interpreter, 2 the lane walk. */
+int wo_dev_ray_form(WoDev* dev);
 /* Progressive accumulation buffer for one rank's share of a width x height
  * frame (row-cyclic tiles of tile_rows rows over nranks; 3 int64 per pixel),
  * zeroed (async, on the device stream) when `reset` or reallocated. */

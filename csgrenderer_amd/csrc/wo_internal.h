@@ -61,6 +61,7 @@ struct Wo_Renderer {
 
     /* compiled program (host copy) */
     WoRec* prog;
+    Wo_Node* prog_nodes; /* per record of prog: the leaf's source node, else WO_NODE_INVALID */
     uint32_t n_recs, n_prims, cap_recs;
     int dirty;          /* nodes/materials changed since the last compile */
     int dev_stale;      /* device copy out of date */
@@ -81,6 +82,7 @@ struct Wo_Renderer {
     uint32_t n_jit_old;
     int jit_async;          /* draw_frame may defer the compile (default; WOLOLO_JIT_ASYNC=0: off) */
     int lanes_loaded;   /* the device runs the lane-traversal kernel */
+    int ray_tracer;     /* Wo_RayTracer: the kernel of ray queries (wo_renderer_trace_rays_device) */
 
     uint64_t frames_drawn;
     uint64_t view_version;  /* bumped by every scene / material / camera change */

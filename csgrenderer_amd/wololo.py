@@ -32,6 +32,10 @@ WORK_KINDS = ("segments", "sphere_tests", "halfspace_tests", "bound_tests", "eve
               "primary_segments", "cyc_take", "cyc_collect", "cyc_sweep", "cyc_shade", "cyc_loop", "idle_lanes",
               "sweep_trips", "cyc_cam")
 WO_NODE_INVALID = 0xFFFFFFFF
+# renderer_ext.h WO_RAY_* (Wo_RayHit.flags) and Wo_RayTracer
+RAY_HIT, RAY_EXIT, RAY_ENTERS, RAY_INVALID = 1, 2, 4, 8
+RAY_TRACER_AUTO, RAY_TRACER_INTERPRETER, RAY_TRACER_LANES = 0, 1, 2
+RAY_TRACERS = {"auto": RAY_TRACER_AUTO, "interpreter": RAY_TRACER_INTERPRETER, "lanes": RAY_TRACER_LANES}
 
 
 class Vec3(Structure):
@@ -74,6 +78,20 @@ class WoFrame(Structure):
                 ("cam", WoCamera), ("band_cycle", c_uint32), ("band_skip", c_uint32)]
 
 
+class Ray(Structure):
+    _fields_ = [("origin", c_float * 3), ("t_max", c_float), ("dir", c_float * 3), ("reserved", c_uint32)]
+
+
+class RayHit(Structure):
+    _fields_ = [("t", c_float), ("flags", c_uint32), ("leaf", c_uint32), ("node", c_uint32),
+                ("normal", c_float * 3), ("material", c_uint32)]
+
+
+# numpy view of a Wo_RayHit array (Renderer.trace_rays returns it)
+RAY_HIT_FIELDS = [("t", "<f4"), ("flags", "<u4"), ("leaf", "<u4"), ("node", "<u4"), ("normal", "<f4", (3,)),
+                  ("material", "<u4")]
+
+assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 32
 assert ctypes.sizeof(Vec3) == 24 and ctypes.sizeof(Quaternion) == 32 and ctypes.sizeof(NodeArgument) == 64
 assert ctypes.sizeof(WoRec) == 32 and ctypes.sizeof(WoMaterial) == 32
 
@@ -142,6 +160,13 @@ SIGNATURES = {
     "wo_renderer_set_jit": (None, [c_void_p, c_int]),
     "wo_renderer_set_tracer": (None, [c_void_p, c_int]),
     "wo_renderer_trace_path": (c_char_p, [c_void_p]),
+    "wo_renderer_trace_rays_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wo_renderer_trace_rays": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+    "wo_renderer_pixel_ray": (c_int, [c_void_p, POINTER(RenderParams), c_uint32, c_uint32, POINTER(Ray)]),
+    "wo_renderer_pick": (c_int, [c_void_p, POINTER(RenderParams), c_uint32, c_uint32, POINTER(RayHit)]),
+    "wo_renderer_program_nodes": (POINTER(c_uint32), [c_void_p, POINTER(c_uint32)]),
+    "wo_renderer_set_ray_tracer": (None, [c_void_p, c_int]),
+    "wo_renderer_ray_path": (c_char_p, [c_void_p]),
     "wo_renderer_set_jit_async": (None, [c_void_p, c_int]),
     "wo_renderer_jit_pending": (c_int, [c_void_p]),
     "wo_renderer_prepare": (c_int, [c_void_p]),
@@ -318,7 +343,7 @@ class Renderer:
 
     def lanes_info(self):
         """The lane tracer's BVH: {"nodes", "depth", "top", "always", "kind"} ("kind": the kernel
-        form of the last path launch, trace_kernels.hip PathKind), or None if not on the lane tracer."""
+        form of the last path or ray launch, trace_kernels.hip PathKind), or None if not on the lane tracer."""
         out = (c_uint32 * 5)()
         if self.lib.wo_renderer_lanes_info(self.ptr, out) < 0:
             return None
@@ -357,6 +382,62 @@ class Renderer:
 
     def trace_path(self) -> str:
         return self.lib.wo_renderer_trace_path(self.ptr).decode()
+
+    # ---- ray queries (renderer_ext.h wo_renderer_trace_rays ...) ----
+    def trace_rays(self, rays):
+        """Trace n rays given as an (n, 8) float32 array of Wo_Ray rows (origin, t_max, dir,
+        reserved); returns a structured array of n Wo_RayHit (RAY_HIT_FIELDS).  Synchronous."""
+        import numpy as np
+        a = np.ascontiguousarray(rays, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays: an (n, 8) float32 array")
+        out = np.zeros(a.shape[0], dtype=np.dtype(RAY_HIT_FIELDS))
+        if self.lib.wo_renderer_trace_rays(self.ptr, a.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p),
+                                           a.shape[0]):
+            raise WololoError(last_error())
+        return out
+
+    def trace_rays_device(self, d_rays: int, d_hits: int, n: int, stream: int = 0):
+        """n Wo_Ray at device address d_rays -> n Wo_RayHit at d_hits, asynchronously on `stream`."""
+        if self.lib.wo_renderer_trace_rays_device(self.ptr, c_void_p(d_rays or None), c_void_p(d_hits or None),
+                                                  int(n), c_void_p(stream or None)):
+            raise WololoError(last_error())
+
+    def pixel_ray(self, params: RenderParams, x: int, y: int):
+        """The pixel-centre ray of a NORMALS frame as a Wo_Ray row: (8,) float32."""
+        import numpy as np
+        ray = Ray()
+        if self.lib.wo_renderer_pixel_ray(self.ptr, ctypes.byref(params), int(x), int(y), ctypes.byref(ray)):
+            raise WololoError(last_error())
+        return np.frombuffer(bytes(ray), dtype=np.float32).copy()
+
+    def pick(self, params: RenderParams, x: int, y: int):
+        """The Wo_RayHit under pixel (x, y): a structured scalar (RAY_HIT_FIELDS)."""
+        import numpy as np
+        hit = RayHit()
+        if self.lib.wo_renderer_pick(self.ptr, ctypes.byref(params), int(x), int(y), ctypes.byref(hit)):
+            raise WololoError(last_error())
+        return np.frombuffer(bytes(hit), dtype=np.dtype(RAY_HIT_FIELDS))[0]
+
+    def program_nodes(self):
+        """Per compiled record its source node handle (WO_NODE_INVALID for non-leaf records)."""
+        import numpy as np
+        n = c_uint32(0)
+        p = self.lib.wo_renderer_program_nodes(self.ptr, ctypes.byref(n))
+        if not p:
+            raise WololoError(last_error())
+        if not n.value:
+            return np.zeros(0, dtype=np.uint32)
+        return np.ctypeslib.as_array(p, shape=(n.value,)).astype(np.uint32)
+
+    def set_ray_tracer(self, tracer):
+        """RAY_TRACER_AUTO / _INTERPRETER / _LANES, or the names "auto", "interpreter", "lanes"."""
+        if isinstance(tracer, str):
+            tracer = RAY_TRACERS[tracer]
+        self.lib.wo_renderer_set_ray_tracer(self.ptr, int(tracer))
+
+    def ray_path(self) -> str:
+        return self.lib.wo_renderer_ray_path(self.ptr).decode()
 
     def frame_desc(self, params: RenderParams, tile_rows=16, rank=0, nranks=1) -> WoFrame:
         fr = WoFrame()

@@ -210,6 +210,70 @@ WoMaterial const* wo_renderer_materials(Wo_Renderer* r, uint32_t* n_materials);
 int wo_renderer_frame_desc(Wo_Renderer* r, Wo_RenderParams const* params, uint32_t tile_rows,
                            uint32_t rank, uint32_t nranks, WoFrame* out);
 
+/* ---- ray queries and picking ----
+ * The tracer behind the frames, asked directly: where does a ray first cross the
+ * surface of the scene's solid, and which node's leaf is that.  A hit is the
+ * first event after WO_T_MIN (wo_scene.h) at which the root's membership
+ * changes -- the path tracer's own segment query, bit for bit. */
+typedef struct Wo_Ray {      /* 32 bytes, 16-byte aligned rows: two 16 B loads per lane */
+    float origin[3];
+    float t_max;             /* a hit is reported only if t <= t_max; +INFINITY = unbounded */
+    float dir[3];            /* used as given; expected unit length, as every ray inside the path tracer */
+    uint32_t reserved;       /* ignored */
+} Wo_Ray;
+
+typedef struct Wo_RayHit {   /* 32 bytes */
+    float t;                 /* ray parameter of the hit (> WO_T_MIN); +INFINITY on a miss */
+    uint32_t flags;          /* WO_RAY_* */
+    uint32_t leaf;           /* index of the hit leaf's record in the compiled program (wo_renderer_program) */
+    Wo_Node node;            /* the sphere / half-space node that leaf was compiled from */
+    float normal[3];         /* outward normal of the CSG solid at the hit (what WO_SHADING_NORMALS encodes) */
+    Wo_Material material;    /* the leaf's material id, clamped as the path tracer clamps it */
+} Wo_RayHit;
+
+#define WO_RAY_HIT      1u   /* the root's membership changes at t */
+#define WO_RAY_EXIT     2u   /* the event is the leaf's far boundary */
+#define WO_RAY_ENTERS   4u   /* the ray enters the solid there (else it leaves it) */
+#define WO_RAY_INVALID  8u   /* non-finite origin or dir, NaN t_max, or dir == 0: not traced */
+
+/* A miss (no hit, a hit beyond t_max, an invalid ray): t = +INFINITY, leaf = node =
+ * material = 0xFFFFFFFF, normal = 0, flags = 0 (WO_RAY_INVALID for an invalid ray).
+ * A hit's normal is the leaf's outward normal at origin + t * dir ((P - c) / r for
+ * a sphere, n for a half-space), negated under WO_RAY_EXIT and negated again
+ * without WO_RAY_ENTERS. */
+
+/* Trace n rays in DEVICE memory into n hits in device memory, on the renderer's
+ * device (wo_renderer_device; whatever wo_renderer_set_devices says),
+ * asynchronously on HIP stream `stream` (NULL = the default stream), ordered as
+ * wo_renderer_render_rows_device is.  Both buffers are 16-byte aligned.  An
+ * edited scene is compiled and uploaded first, as by a render.  n = 0 launches
+ * nothing.  0, or -1 (last_error; always for a device-less renderer). */
+int wo_renderer_trace_rays_device(Wo_Renderer* r, Wo_Ray const* d_rays, Wo_RayHit* d_hits, size_t n, void* stream);
+/* The same from and to host memory (synchronous; includes both copies). */
+int wo_renderer_trace_rays(Wo_Renderer* r, Wo_Ray const* rays, Wo_RayHit* hits, size_t n);
+/* The ray a WO_SHADING_NORMALS frame of params' size traces through pixel (x, y)
+ * (row 0 = top) with the current camera: the pixel centre, no lens offset,
+ * t_max = +INFINITY.  Host arithmetic, no device needed.  -1 outside the frame. */
+int wo_renderer_pixel_ray(Wo_Renderer* r, Wo_RenderParams const* params, uint32_t x, uint32_t y, Wo_Ray* out);
+/* What lies under pixel (x, y): pixel_ray, then a one-ray trace_rays. */
+int wo_renderer_pick(Wo_Renderer* r, Wo_RenderParams const* params, uint32_t x, uint32_t y, Wo_RayHit* out);
+/* Per record of the compiled program (wo_renderer_program) the node it was
+ * compiled from: the sphere / half-space node for WO_LEAF_* records (every
+ * instance of a node used several times names that node), WO_NODE_INVALID for
+ * all others.  Valid until the next node / material change. */
+Wo_Node const* wo_renderer_program_nodes(Wo_Renderer* r, uint32_t* n_recs);
+/* Kernel of the ray queries (results are identical; only speed differs):
+ *   AUTO         LANES where it applies, else INTERPRETER;
+ *   INTERPRETER  the postfix-program interpreter, one wave walking the program
+ *                for its 64 rays (any scene; best for coherent rays);
+ *   LANES        per-lane BVH traversal (union-only scenes; others fall back to
+ *                the interpreter).
+ * The scene-specialised kernel is not used for ray queries. */
+typedef enum Wo_RayTracer { WO_RAY_TRACER_AUTO = 0, WO_RAY_TRACER_INTERPRETER = 1, WO_RAY_TRACER_LANES = 2 } Wo_RayTracer;
+void wo_renderer_set_ray_tracer(Wo_Renderer* r, Wo_RayTracer tracer);
+/* Which kernel the last ray launch used: "interpreter", "lanes" or "none". */
+char const* wo_renderer_ray_path(Wo_Renderer* r);
+
 /* Path-tracer kernel selection (results are identical; only speed differs).
  *   AUTO         union-only scenes of more than WOLOLO_LANES_MIN_PRIMS (256)
  *                primitives -> LANES; else scenes of up to WOLOLO_JIT_MAX_PRIMS
@@ -280,9 +344,10 @@ int wo_renderer_jit_info(Wo_Renderer* r, double* seconds);
 /* The lane tracer's BVH (union-only scenes): out[0] internal nodes, out[1] its
  * depth in internal levels (= the per-lane LDS stack entries; at most 24),
  * out[2] top nodes staged in LDS, out[3] primitives tested on every query (no
- * box), out[4] the kernel form of the last path launch (0-14 the lane tracer's
+ * box), out[4] the kernel form of the last path or ray launch (0-14 the lane tracer's
  * forms, 11-14 the resumable walk; trace_kernels.hip PathKind).  `out` holds 5
- * entries.  Returns 0, or -1 when the renderer does not run the lane tracer. */
+ * entries.  Returns 0, or -1 when the renderer does not run the lane tracer
+ * (neither its path kernel nor its last ray query). */
 int wo_renderer_lanes_info(Wo_Renderer* r, uint32_t* out);
 /* The path kernel of the last launch as the runtime loaded it: key_hex (65 bytes)
  * gets the specialised kernel's code-object key (SHA-256 of source, options and
@@ -303,7 +368,7 @@ void wo_renderer_clear_error(void);
 /* ---- library-level ---- */
 /* sizeof(type) (field NULL) or offsetof(type, field) as this library was
  * compiled, for the value types of the C ABI (Wo_Vec3, Wo_Quaternion,
- * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame);
+ * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame, Wo_Ray, Wo_RayHit);
  * (size_t)-1 for an unknown name.  Bindings check their mirrors with it. */
 size_t wo_abi_layout(char const* type, char const* field);
 /* Device self-check of the path tracer's fast correctly rounded square root
