@@ -289,24 +289,16 @@ struct InterpTracer {
 };
 
 // ---------------------------------------------------------------------------
-// Lane traversal, for programs whose every binop is a UNION (scenes like the
-// RTIOW cover: hundreds of primitives, no CSG).  Each lane walks the BOUND
-// hierarchy on its own (stackless: a missed BOUND jumps to its skip target),
-// so a wave costs the LONGEST lane's walk instead of the UNION of its lanes'
-// walks -- the difference that matters for incoherent bounce rays.  The trav
-// table is the program with the binop records dropped (host: build_trav).
-//
-// Union semantics need no tree evaluation: the root is inside iff the count
-// of primitives containing the point is > 0; an entry event adds one, an exit
-// removes one.  A BOUND whose near end (tca - R, with slack) lies beyond the
-// nearest event collected so far is pruned; the sweep treats the smallest
-// pruned near end as a barrier (`kcut`): reaching it re-collects after the
-// last processed event, exactly as an overflowing window does.  Results are
-// the general algorithm's, bit for bit.
+// Lane traversal (scenes like the RTIOW cover: hundreds of primitives).  Each
+// lane walks a hierarchy on its own, so a wave costs the LONGEST lane's walk
+// instead of the UNION of its lanes' walks -- the difference that matters for
+// incoherent bounce rays.  Union semantics need no tree evaluation: the root is
+// inside iff the count of primitives containing the point is > 0; an entry event
+// adds one, an exit removes one.  Results are the general algorithm's, bit for bit.
 // ---------------------------------------------------------------------------
 
 // Ordered BVH traversal (the common case).  The host builds a binary AABB
-// hierarchy over the bounded primitives (build_lbvh; each node holds its two
+// hierarchy over the bounded primitives (lane_bvh_build.cpp; each node holds its two
 // children's boxes, expanded outward), and an `always` list of the unbounded
 // and outsized ones.  A lane walks it nearest child first with a short LDS
 // stack and prunes every box whose near end lies beyond the nearest entry event
@@ -317,18 +309,9 @@ struct InterpTracer {
 // depend on the visiting order, so the result is the general algorithm's bit for
 // bit.  A ray that starts inside some primitive (counted on the way: boxes that
 // contain the ray's start are never pruned) takes the general walk below.
-constexpr uint32_t kLeafRef = 0x80000000u, kNoRef = 0xffffffffu;
-// 16-bit refs (lane stacks, 4-wide nodes): node index or ordinal in bits 0-14, leaf flag in bit 15
-constexpr uint32_t kNoRef16 = 0xffffu;
-// term mode (extract_terms): literals per term; a literal is ordinal | kLitNeg (complement)
-constexpr uint32_t kTermLits = 2, kLitNeg = 0x80000000u, kNoLit = 0xffffffffu;
-// term records (build_lbvh): float4 [0] = literal 0, literal 1, kinds (2 bits per
-// literal), 0; [1 + 2x], [2 + 2x] = literal x's sphere members (centre, r^2)
-constexpr uint32_t kTermRecF4 = 5, kTermLitSphere = 1, kTermLitSphere2 = 2;  // kind 0: generic (prim_ivl)
-// The lane BVH is built with at most kLaneDepthMax internal levels on any path,
-// and the per-lane LDS stack holds as many entries as the built tree has levels:
-// a walk pushes at most one sibling per ancestor, so the stack never overflows.
-constexpr uint32_t kLaneDepthMax = 24;
+// The refs, literals and term records are lane_bvh.h's.
+using namespace wolbvh;
+static_assert(kLaneBlock == kBlock, "the lane BVH's LDS is sized for the kernels' workgroup");
 #ifndef WO_LANES_TERM2
 #define WO_LANES_TERM2 1  // term visits of two spheres in all: two sphere tests (visit_leaf)
 #endif
@@ -344,18 +327,6 @@ constexpr uint32_t kLaneDepthMax = 24;
 #ifndef WO_LANES_FUSED_SPHERE
 #define WO_LANES_FUSED_SPHERE 1
 #endif
-// dynamic LDS of the BVH walk (stacks + top nodes): with the kernel's static LDS,
-// 8 workgroups of kBlock fit in a CU's 160 KB
-#ifndef WO_LANES_CAM
-#define WO_LANES_CAM 0  // the lane kernels' camera-wave mode (pathtrace_block kCam)
-#endif
-// the camera ring's LDS per workgroup (64 slots of 48 B per wave)
-constexpr size_t kCamRingLds = WO_LANES_CAM ? 4u * 64u * 48u : 0u;
-// 8 workgroups per CU = 20 KB each, less the kernels' static LDS (2224 B since the
-// pixel-row table, round 5; at 18 KB of dynamic LDS the total crossed 20 KB and the
-// RTIOW cover ran at 7 workgroups per CU: 11.24 -> 11.69 ms)
-constexpr size_t kLanesStaticLdsMax = 2304u;
-constexpr size_t kLanesBvhLds = 20u * 1024u - kLanesStaticLdsMax;
 
 // component c (a compile-time constant after unrolling) of a float4
 __device__ __forceinline__ float f4c(const float4& v, int c) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); }
@@ -372,16 +343,13 @@ __device__ __forceinline__ float box_near(float4 lo, float4 hi, F3 ri, F3 oi, fl
     return n;
 }
 
-// The same over a child box stored as fp16 (lb_half: lo rounded down, hi up, so
-// the box only grows): q.x = lo.x | lo.y << 16, q.y = lo.z | hi.x << 16, q.z =
-// hi.y | hi.z << 16.  The conversions fold into v_fma_mix_f32.
 // kMode (PathKind): 2 ordered BVH over union-only primitives, 3 the same over
 // single-sphere primitives only (no generic-primitive code: fewer registers),
 // 6 ordered BVH over the terms of a root that is a union of small conjunctions
-// (extract_terms: the leaves and the always list hold terms), 7 ordered BVH over
+// (the leaves and the always list hold terms), 7 ordered BVH over
 // the primitives of a general tree (the events in key order, kGWin per walk, and
 // the tree's value kept per lane and updated along the toggled leaf's path), 14 term mode over a
-// 4-wide tree (lb_collapse4: four child boxes per node, half the dependent node
+// 4-wide tree (four child boxes per node, half the dependent node
 // loads of a walk; 16-bit stacks) with the resumable walk (trace_step, dynamic
 // ray fetch).  Measured and removed: the general BOUND walk,
 // 16-bit stacks for binary trees, 4-wide trees for primitives, resumable binary
@@ -401,8 +369,6 @@ constexpr int kGWin = WO_LANES_GWIN;
 #ifndef WO_LANES_TRIP_LEAVES
 #define WO_LANES_TRIP_LEAVES 1
 #endif
-// a general tree's node record (build_lbvh): left ref | right ref << 15 | op << 30
-constexpr uint32_t kGRefBits = 15u, kGRefMask = (1u << kGRefBits) - 1u;
 template <int kModeT, bool kCountT>
 struct LaneTracer {
     static_assert(kModeT == 2 || kModeT == 3 || kModeT == 6 || kModeT == 7 || kModeT == 14, "lane tracer forms");
@@ -424,7 +390,7 @@ struct LaneTracer {
     uint64_t tmark;  // section timing (counting builds)
     const WoRec* __restrict__ prog;      // full program (generic primitives, hit leaves)
     const uint32_t* __restrict__ ordpc;  // ordinal -> program pc
-    // ordered BVH (build_lbvh)
+    // ordered BVH (lane_bvh.h)
     const float4* __restrict__ lnodes;   // 4 float4 per node: childA lo|ref, childA hi|ref B, childB lo, childB hi
     const float4* __restrict__ lgeo;     // per ordinal: sphere centre, r^2 (single-sphere primitives)
     const uint32_t* __restrict__ lkind;  // per ordinal: 1 = single sphere, 0 = generic; then the always list
@@ -666,7 +632,7 @@ struct LaneTracer {
 #endif
         Ivl iv = prim_ivl(ord, o, d, inv, have_inv);
         if constexpr (kGeneral) {
-            // The primitive restricted to its relevance box (build_lbvh): outside it the
+            // The primitive restricted to its relevance box (lane_bvh_build.cpp): outside it the
             // primitive cannot change the root (an intersection's other operand, or a
             // difference's left one, is empty there), so its interval is clipped to the
             // box's span, widened by a margin past the slab test's rounding.  An end
@@ -857,10 +823,10 @@ struct LaneTracer {
                     const bool a_first = na <= nb;
                     cur = a_first ? ra : rb;
                     const uint32_t other = a_first ? rb : ra;
-                    if constexpr (kStack16)  // refs < 2^15 (build_lbvh): the leaf flag moves to bit 15
+                    if constexpr (kStack16)  // refs < 2^15 (the builder's check): the leaf flag moves to bit 15
                         stk16[sp * kBlock] = (uint16_t)((other & 0x7fffu) | ((other >> 16) & 0x8000u));
                     else
-                        stk[sp * kBlock] = other;  // sp < the tree's depth (build_lbvh)
+                        stk[sp * kBlock] = other;  // sp < the tree's depth (kLaneDepthMax)
                     ++sp;
                 } else {
                     cur = ha ? ra : (hb ? rb : kNoRef);
@@ -1067,7 +1033,7 @@ struct LaneTracer {
 #ifndef WO_LANES_MIN_WAVES
 #define WO_LANES_MIN_WAVES 8  // rtiow_cover: 40.0 ms at 6, 37.4 at 7, 36.5 at 8 (64 VGPRs)
 #endif
-// The ordered-BVH tables of a union-only program (build_lbvh).
+// The ordered-BVH tables (the sections of lane_bvh.h's blob, on the device).
 struct LaneBvh {
     const float4* nodes;
     const float4* geo;
@@ -1578,20 +1544,11 @@ struct WoDev {
     // lane tracer: ordinal -> program pc (generic primitives, hit leaves)
     uint32_t* d_ordpc;
     size_t ordpc_cap;
-    // the lane tracer's ordered BVH (build_lbvh): [4 float4 per node][float4 per
-    // ordinal] then u32 [kind per ordinal][always list]
+    // the lane tracer's ordered BVH: the builder's blob and its descriptor (lane_bvh.h)
     float4* d_lbvh;
     size_t lbvh_cap;
-    uint32_t lb_nodes, lb_always, lb_root, lb_nprims;
-    bool lb_spheres_only;  // every primitive is a single sphere (kind 3)
-    bool lb_stack16;       // 16-bit stack entries (the 4-wide tree)
-    bool lb_wide;          // 4-wide nodes of 7 float4 (lb_collapse4; kind 14)
-    uint32_t lb_terms;     // term mode (kinds 6 / 14): terms the BVH's leaves and always list refer to
-    bool lb_general;       // a general tree (kind 7): the BVH over primitives, the tree's tables below
-    uint32_t lb_gpar_off, lb_gnode_off;  // u32 offsets in d_lbvh of the parent per ref / node records
-    uint32_t lb_gclip_off;               // u32 offset of the primitives' relevance boxes (0: none)
-    uint32_t lb_gP, lb_gwords, lb_groot;  // leaves (= primitives), bit words per lane, the root's ref
-    uint32_t last_kind;    // the PathKind of the last path launch (wo_dev_lanes_info)
+    WoLaneBvhDesc lbvh;
+    uint32_t last_kind;   // the PathKind of the last path launch (wo_dev_lanes_info)
     // ray queries (wo_dev_trace_rays): per program record its source node handle, the
     // host form's staging buffer (rays, then hits), and the last ray launch's kernel
     uint32_t* d_nodes;
@@ -1601,10 +1558,6 @@ struct WoDev {
     size_t rayio_cap;
     uint32_t ray_kind;     // its PathKind (kLanesBvh / kLanesBvhSpheres / kInterpLds / kInterpGlobal; 0: none yet)
     bool ray_last;         // the last path or ray launch was a ray launch (wo_dev_lanes_info's form)
-    uint32_t lb_term_off;  // their records (kTermRecF4 float4 each) at this u32 offset of d_lbvh
-    uint32_t lb_leaf_off;  // single-sphere scenes: per ordinal its leaf record (WoRec) at this u32 offset, else 0
-    uint32_t lb_top;       // nodes staged in LDS per workgroup
-    uint32_t lb_depth;     // internal levels of the lane BVH (<= kLaneDepthMax)
     unsigned long long* d_segslots;  // kSegSlots segment counters, kSegStride apart
     unsigned long long* d_work;      // WO_WORK_KINDS totals of a counting launch
     // progressive accumulation (3 int64 per pixel) and the frame slots (wo_dev.h
@@ -1659,7 +1612,6 @@ struct WoDev {
     hipEvent_t psrc_ev[WO_SLOTS], penc_ev[WO_SLOTS], pmap_ev[WO_SLOTS];
     int peer_mode;  // how this rank's share reaches the root (WO_PEER_*; wo_dev_enable_peer)
     unsigned long long* d_segacc;  // segments of this rank's device frames (wo_dev_take_segments)
-    bool union_only;
     bool lanes_on;
     // scene-specialised kernel (hiprtc)
     hipModule_t jit_module;
@@ -1803,776 +1755,20 @@ static int ensure_buffer(T** p, size_t* cap, size_t bytes, char* err, size_t err
     return 0;
 }
 
-// Whether the program is union-only (the lane tracer's union count), and the
-// ordinal -> program pc map the lane tracer reads generic primitives and hit
-// leaves through.
-static int scene_maps(WoDev* dev, WoRec const* prog, uint32_t n_recs, uint32_t n_prims, char* err, size_t errlen) {
-    bool union_only = n_prims > 0;
-    std::vector<uint32_t> ordpc(n_prims ? n_prims : 1u, 0u);
-    for (uint32_t pc = 0; pc < n_recs;) {
-        const uint32_t op = prog[pc].op;
-        if (op == WO_OP_PRIM) {
-            if (prog[pc].u1 < n_prims) ordpc[prog[pc].u1] = pc;
-            pc += 1u + prog[pc].u0;
-        } else {
-            if (op != WO_OP_UNION && op != WO_OP_BOUND) union_only = false;
-            ++pc;
-        }
-    }
-    dev->union_only = union_only;
-    if (ensure_buffer(&dev->d_ordpc, &dev->ordpc_cap, ordpc.size() * sizeof(uint32_t), err, errlen)) return -1;
-    hipError_t e = hipMemcpy(dev->d_ordpc, ordpc.data(), ordpc.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_err(err, errlen, "hipMemcpy(ordinal map)", e);
-        return -1;
-    }
-    return 0;
-}
-
-// ---- the lane tracer's ordered BVH ----
-// Axis-aligned box of a convex primitive from its members (spheres, axis-aligned
-// half-spaces; general planes bound nothing), in double; false if unbounded or
-// empty.
-static bool prim_aabb(WoRec const* prog, uint32_t pc, double lo[3], double hi[3]) {
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = -INFINITY;
-        hi[a] = INFINITY;
-    }
-    for (uint32_t m = 0; m < prog[pc].u0; ++m) {
-        const WoRec& L = prog[pc + 1u + m];
-        if (L.op == WO_LEAF_SPHERE) {
-            const double r = sqrt((double)L.f[3]);
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = fmax(lo[a], (double)L.f[a] - r);
-                hi[a] = fmin(hi[a], (double)L.f[a] + r);
-            }
-        } else if (L.op == WO_LEAF_HALFSPACE && L.u1 >= 1u && L.u1 <= 3u) {
-            const int a = (int)L.u1 - 1;  // s * x_a <= h
-            if (L.f[a] > 0.0f)
-                hi[a] = fmin(hi[a], (double)L.f[3]);
-            else
-                lo[a] = fmax(lo[a], -(double)L.f[3]);
-        }
-    }
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || lo[a] > hi[a]) return false;
-    return true;
-}
-
-struct LbPrim {
-    double lo[3], hi[3], c[3];
-    uint32_t ord;
-};
-
-struct LbBox {
-    double lo[3], hi[3];
-    void empty() {
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = INFINITY;
-            hi[a] = -INFINITY;
-        }
-    }
-    void grow(const double* l, const double* h) {
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fmin(lo[a], l[a]);
-            hi[a] = fmax(hi[a], h[a]);
-        }
-    }
-    double area() const {
-        const double x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
-        return x < 0.0 ? 0.0 : 2.0 * (x * y + y * z + z * x);
-    }
-};
-
-static uint32_t ceil_log2(uint32_t c) {
-    uint32_t k = 0;
-    while ((1ull << k) < c) ++k;
-    return k;
-}
-
-// Binned-SAH build over prims[b, e) with at most `levels` internal levels below
-// (ceil_log2(e - b) <= levels on entry); returns the subtree's ref and its
-// depth.  A SAH split that would leave a child more primitives than its levels
-// can hold becomes the median split, which always fits.  Node n is written to
-// nodes[4n..4n+3] as the two children's boxes (rounded outward to float) with
-// their refs in the .w of the first two.
-static uint32_t lb_build(std::vector<LbPrim>& prims, uint32_t b, uint32_t e, uint32_t levels,
-                         std::vector<float4>& nodes, LbBox& box_out, uint32_t& depth_out) {
-    box_out.empty();
-    for (uint32_t i = b; i < e; ++i) box_out.grow(prims[i].lo, prims[i].hi);
-    depth_out = 0;
-    if (e - b == 1u) return kLeafRef | prims[b].ord;
-    LbBox cb;
-    cb.empty();
-    for (uint32_t i = b; i < e; ++i) cb.grow(prims[i].c, prims[i].c);
-    int axis = 0;
-    for (int a = 1; a < 3; ++a)
-        if (cb.hi[a] - cb.lo[a] > cb.hi[axis] - cb.lo[axis]) axis = a;
-    uint32_t mid = b + (e - b) / 2u;
-    const double ext = cb.hi[axis] - cb.lo[axis];
-    if (ext > 0.0) {
-        constexpr int kBins = 16;
-        LbBox bb[kBins];
-        uint32_t bn[kBins] = {};
-        for (int k = 0; k < kBins; ++k) bb[k].empty();
-        auto bin_of = [&](const LbPrim& p) {
-            int k = (int)((p.c[axis] - cb.lo[axis]) / ext * kBins);
-            return k < 0 ? 0 : (k >= kBins ? kBins - 1 : k);
-        };
-        for (uint32_t i = b; i < e; ++i) {
-            const int k = bin_of(prims[i]);
-            bb[k].grow(prims[i].lo, prims[i].hi);
-            ++bn[k];
-        }
-        double best = INFINITY;
-        int split = -1;
-        for (int s = 1; s < kBins; ++s) {
-            LbBox l, r;
-            l.empty();
-            r.empty();
-            uint32_t nl = 0, nr = 0;
-            for (int k = 0; k < s; ++k) l.grow(bb[k].lo, bb[k].hi), nl += bn[k];
-            for (int k = s; k < kBins; ++k) r.grow(bb[k].lo, bb[k].hi), nr += bn[k];
-            if (!nl || !nr) continue;
-            const double cost = l.area() * nl + r.area() * nr;
-            if (cost < best) best = cost, split = s;
-        }
-        if (split > 0) {
-            auto it = std::partition(prims.begin() + b, prims.begin() + e,
-                                     [&](const LbPrim& p) { return bin_of(p) < split; });
-            mid = (uint32_t)(it - prims.begin());
-        }
-    }
-    if (mid == b || mid == e || ceil_log2(mid - b) >= levels || ceil_log2(e - mid) >= levels) {
-        // no useful split, or one too deep for the lane stack: the median along the axis
-        mid = b + (e - b) / 2u;
-        std::nth_element(prims.begin() + b, prims.begin() + mid, prims.begin() + e,
-                         [&](const LbPrim& x, const LbPrim& y) { return x.c[axis] < y.c[axis]; });
-    }
-    const uint32_t n = (uint32_t)(nodes.size() / 4u);
-    nodes.resize(nodes.size() + 4u);
-    LbBox lb, rb;
-    uint32_t ld, rd;
-    const uint32_t lref = lb_build(prims, b, mid, levels - 1u, nodes, lb, ld);
-    const uint32_t rref = lb_build(prims, mid, e, levels - 1u, nodes, rb, rd);
-    depth_out = 1u + (ld > rd ? ld : rd);
-    auto bits_f = [](uint32_t u) {
-        float f;
-        memcpy(&f, &u, sizeof f);
-        return f;
-    };
-    auto down = [](double v) { return nextafterf((float)v, -INFINITY); };
-    auto up = [](double v) { return nextafterf((float)v, INFINITY); };
-    float4* q = &nodes[4u * n];
-    q[0] = make_float4(down(lb.lo[0]), down(lb.lo[1]), down(lb.lo[2]), bits_f(lref));
-    q[1] = make_float4(up(lb.hi[0]), up(lb.hi[1]), up(lb.hi[2]), bits_f(rref));
-    q[2] = make_float4(down(rb.lo[0]), down(rb.lo[1]), down(rb.lo[2]), 0.0f);
-    q[3] = make_float4(up(rb.hi[0]), up(rb.hi[1]), up(rb.hi[2]), 0.0f);
-    return n;
-}
-
-// 4-wide tree from lb_build's binary one (refs before the breadth-first order):
-// a node takes its two children and, while it has fewer than four, replaces the
-// internal child of largest surface area by that child's two children.  Node n
-// is written to n4[7n..7n+6]: lo.x, hi.x, lo.y, hi.y, lo.z, hi.z of the four
-// children (the binary nodes' expanded, outward-rounded boxes), then their refs
-// (kNoRef for an empty slot; lb_bfs4 turns them into 16-bit refs, kNoRef16).
-// `levels` = internal levels on the longest path.
-struct Lb4Child {
-    float lo[3], hi[3];
-    uint32_t ref;
-    double area() const {
-        const double x = (double)hi[0] - lo[0], y = (double)hi[1] - lo[1], z = (double)hi[2] - lo[2];
-        return 2.0 * (x * y + y * z + z * x);
-    }
-};
-static void lb_children2(const std::vector<float4>& n2, uint32_t n, Lb4Child out[2]) {
-    const float4* q = &n2[4u * n];
-    const float4 lo[2] = {q[0], q[2]}, hi[2] = {q[1], q[3]};
-    for (int c = 0; c < 2; ++c) {
-        out[c].lo[0] = lo[c].x, out[c].lo[1] = lo[c].y, out[c].lo[2] = lo[c].z;
-        out[c].hi[0] = hi[c].x, out[c].hi[1] = hi[c].y, out[c].hi[2] = hi[c].z;
-        memcpy(&out[c].ref, c == 0 ? &q[0].w : &q[1].w, sizeof(uint32_t));
-    }
-}
-static uint32_t lb_collapse4(const std::vector<float4>& n2, uint32_t n, std::vector<float4>& n4, uint32_t& levels) {
-    std::vector<Lb4Child> ch(2);
-    lb_children2(n2, n, ch.data());
-    while (ch.size() < 4u) {
-        int pick = -1;
-        double best = -1.0;
-        for (int i = 0; i < (int)ch.size(); ++i)
-            if (!(ch[i].ref & kLeafRef) && ch[i].area() > best) best = ch[i].area(), pick = i;
-        if (pick < 0) break;
-        Lb4Child sub[2];
-        lb_children2(n2, ch[pick].ref, sub);
-        ch[pick] = sub[0];
-        ch.push_back(sub[1]);
-    }
-    const uint32_t me = (uint32_t)(n4.size() / 7u);
-    n4.resize(n4.size() + 7u);
-    levels = 1u;
-    uint32_t refs[4];
-    for (uint32_t i = 0; i < 4u; ++i) {
-        if (i >= ch.size()) {
-            refs[i] = kNoRef;
-        } else if (ch[i].ref & kLeafRef) {
-            refs[i] = ch[i].ref;
-        } else {
-            uint32_t lv = 0;
-            refs[i] = lb_collapse4(n2, ch[i].ref, n4, lv);
-            levels = std::max(levels, 1u + lv);
-        }
-    }
-    float v[7][4];
-    for (uint32_t i = 0; i < 4u; ++i) {
-        const bool has = i < ch.size();
-        for (int a = 0; a < 3; ++a) {
-            v[2 * a][i] = has ? ch[i].lo[a] : 0.0f;
-            v[2 * a + 1][i] = has ? ch[i].hi[a] : 0.0f;
-        }
-        memcpy(&v[6][i], &refs[i], sizeof(float));  // full refs here; 16-bit after lb_bfs4
-    }
-    for (int k = 0; k < 7; ++k) n4[7u * me + (uint32_t)k] = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
-    return me;
-}
-// breadth-first order of a 4-wide tree rooted at node `root` (the root becomes 0)
-static void lb_bfs4(std::vector<float4>& n4, uint32_t root) {
-    const uint32_t nn = (uint32_t)(n4.size() / 7u);
-    auto ref_at = [&](uint32_t n, int c) {
-        uint32_t u;
-        memcpy(&u, reinterpret_cast<const float*>(&n4[7u * n + 6u]) + c, sizeof u);
-        return u;
-    };
-    std::vector<uint32_t> order, newidx(nn, 0u);
-    order.push_back(root);
-    for (size_t h = 0; h < order.size(); ++h)
-        for (int c = 0; c < 4; ++c) {
-            const uint32_t r = ref_at(order[h], c);
-            if (r != kNoRef && !(r & kLeafRef)) order.push_back(r);
-        }
-    for (uint32_t i = 0; i < nn; ++i) newidx[order[i]] = i;
-    std::vector<float4> bfs(n4.size());
-    for (uint32_t i = 0; i < nn; ++i) {
-        for (int k = 0; k < 7; ++k) bfs[7u * i + (uint32_t)k] = n4[7u * order[i] + (uint32_t)k];
-        for (int c = 0; c < 4; ++c) {
-            uint32_t r = ref_at(order[i], c);
-            if (r != kNoRef && !(r & kLeafRef)) r = newidx[r];
-            // 16-bit form (the kernel's sort keys and stack entries; refs < 2^15 checked by the caller)
-            r = r == kNoRef ? kNoRef16 : ((r & 0x7fffu) | ((r >> 16) & 0x8000u));
-            memcpy(reinterpret_cast<float*>(&bfs[7u * i + 6u]) + c, &r, sizeof r);
-        }
-    }
-    n4.swap(bfs);
-}
-
-// ---- union of conjunctions (the lane tracer's term mode) ----
-// A program whose root is a union of TERMS, each a conjunction of at most
-// kTermLits literals (a primitive or its complement: a DIFF of one primitive by
-// another is a AND NOT b) and each primitive in one term: csg256 / csg512
-// balanced's pairs, csg32's box minus sphere.  Along a ray, a term's value can
-// only change at an event of its own literals, so the root (a union) changes
-// exactly when the count of true terms crosses 0 -- the union-only sweep with
-// term transitions in place of primitive events (LaneTracer::visit_term).
-// Literal encoding: ordinal | kLitNeg for a complement.
-
-struct TermSub {
-    int kind;  // 0 conjunction (lits), 1 union of conjunctions (terms), 2 not expressible
-    std::vector<uint32_t> lits;
-    std::vector<std::vector<uint32_t>> terms;
-};
-
-// The root's terms, or false when the program is not such a union.
-static bool extract_terms(WoRec const* prog, uint32_t n_recs, uint32_t n_prims,
-                          std::vector<std::vector<uint32_t>>& terms) {
-    std::vector<TermSub> st;
-    auto bad = []() { TermSub t; t.kind = 2; return t; };
-    auto as_terms = [](const TermSub& x) {
-        return x.kind == 0 ? std::vector<std::vector<uint32_t>>{x.lits} : x.terms;
-    };
-    // NOT of a union of single positive literals (a difference's right operand)
-    auto negated = [](const TermSub& x, std::vector<uint32_t>& out) {
-        if (x.kind == 0) {
-            if (x.lits.size() != 1u || (x.lits[0] & kLitNeg)) return false;
-            out.push_back(x.lits[0] | kLitNeg);
-            return true;
-        }
-        if (x.kind != 1) return false;
-        for (const auto& t : x.terms) {
-            if (t.size() != 1u || (t[0] & kLitNeg)) return false;
-            out.push_back(t[0] | kLitNeg);
-        }
-        return true;
-    };
-    for (uint32_t pc = 0; pc < n_recs;) {
-        const WoRec& r = prog[pc];
-        if (r.op == WO_OP_PRIM) {
-            TermSub t;
-            t.kind = 0;
-            t.lits.push_back(r.u1);
-            st.push_back(t);
-            pc += 1u + r.u0;
-            continue;
-        }
-        ++pc;
-        if (r.op == WO_OP_BOUND) continue;  // a culling hint: evaluators may ignore it
-        if (st.size() < 2u) return false;
-        TermSub b = st.back();
-        st.pop_back();
-        TermSub a = st.back();
-        st.pop_back();
-        TermSub out = bad();
-        if (a.kind != 2 && b.kind != 2) {
-            if (r.op == WO_OP_UNION) {
-                out.kind = 1;
-                out.terms = as_terms(a);
-                const auto tb = as_terms(b);
-                out.terms.insert(out.terms.end(), tb.begin(), tb.end());
-            } else if (r.op == WO_OP_INTER && a.kind == 0 && b.kind == 0) {
-                out.kind = 0;
-                out.lits = a.lits;
-                out.lits.insert(out.lits.end(), b.lits.begin(), b.lits.end());
-            } else if ((r.op == WO_OP_DIFF || r.op == WO_OP_RDIFF)) {
-                const TermSub& keep = r.op == WO_OP_DIFF ? a : b;  // DIFF: a AND NOT b; RDIFF: b AND NOT a
-                const TermSub& sub = r.op == WO_OP_DIFF ? b : a;
-                std::vector<uint32_t> neg;
-                if (keep.kind == 0 && negated(sub, neg)) {
-                    out.kind = 0;
-                    out.lits = keep.lits;
-                    out.lits.insert(out.lits.end(), neg.begin(), neg.end());
-                }
-            }
-        }
-        st.push_back(out);
-    }
-    if (st.size() != 1u || st[0].kind == 2) return false;
-    terms = as_terms(st[0]);
-    std::vector<uint8_t> seen(n_prims, 0);
-    for (const auto& t : terms) {
-        if (t.empty() || t.size() > kTermLits) return false;
-        for (uint32_t l : t) {
-            const uint32_t o = l & ~kLitNeg;
-            if (o >= n_prims || seen[o]) return false;  // one term per primitive
-            seen[o] = 1;
-        }
-    }
-    return true;
-}
-
-static uint32_t lb_node_f4(const WoDev* dev) { return dev->lb_wide ? 7u : 4u; }
-
-static int build_lbvh(WoDev* dev, WoRec const* prog, uint32_t n_recs, uint32_t n_prims, WoMaterial const* mats,
-                      uint32_t n_mats, char* err, size_t errlen) {
-    dev->lb_nodes = dev->lb_always = dev->lb_top = dev->lb_depth = 0;
-    dev->lb_root = kNoRef;
-    dev->lb_nprims = n_prims;
-    dev->lb_spheres_only = false;
-    dev->lb_stack16 = false;
-    dev->lb_wide = false;
-    dev->lb_terms = 0;
-    dev->lb_general = false;
-    // not union-only: the BVH over the root's terms, when the root is a union of
-    // small conjunctions (extract_terms); else over the primitives of the general tree,
-    // whose value the lanes keep (gpar / gnode: the tree over the primitives, BOUND
-    // records dropped; refs [0, P) the primitives' leaves, [P, P + nodes) the binops)
-    std::vector<std::vector<uint32_t>> terms;
-    std::vector<uint32_t> gpar, gnode;
-    uint32_t groot = kNoRef;
-    if (!dev->union_only && !extract_terms(prog, n_recs, n_prims, terms)) {
-        if (!n_prims) return 0;
-        gpar.assign(n_prims, kNoRef);
-        std::vector<uint32_t> st;
-        for (uint32_t pc = 0; pc < n_recs;) {
-            const WoRec& r = prog[pc];
-            if (r.op == WO_OP_PRIM) {
-                st.push_back(r.u1);
-                pc += 1u + r.u0;
-                continue;
-            }
-            ++pc;
-            if (r.op == WO_OP_BOUND) continue;
-            if (st.size() < 2u) {
-                snprintf(err, errlen, "malformed program (binop without operands)");
-                return -1;
-            }
-            const uint32_t b = st.back();
-            st.pop_back();
-            const uint32_t a = st.back();
-            st.pop_back();
-            const uint32_t op = r.op == WO_OP_UNION ? 0u : r.op == WO_OP_INTER ? 1u : r.op == WO_OP_DIFF ? 2u : 3u;
-            const uint32_t n = n_prims + (uint32_t)gnode.size();
-            gnode.push_back(a | (b << kGRefBits) | (op << 30));
-            gpar.push_back(kNoRef);
-            gpar[a] = n;
-            gpar[b] = n;
-            st.push_back(n);
-        }
-        if (st.size() != 1u || gpar.size() > kGRefMask) return 0;  // (refs beyond 15 bits: no lane form)
-        groot = st[0];
-        dev->lb_general = true;
-    }
-    std::vector<LbPrim> prims;
-    std::vector<uint32_t> always;
-    std::vector<float4> geo(n_prims, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    std::vector<uint32_t> kind(n_prims, 0u);
-    std::vector<uint32_t> pc_of(n_prims, 0u);
-    for (uint32_t pc = 0; pc < n_recs;) {
-        const WoRec& r = prog[pc];
-        if (r.op != WO_OP_PRIM) {
-            ++pc;
-            continue;
-        }
-        const uint32_t ord = r.u1;
-        if (ord >= n_prims) {
-            snprintf(err, errlen, "primitive ordinal out of range");
-            return -1;
-        }
-        const WoRec& L = prog[pc + 1u];
-        if (r.u0 == 1u && L.op == WO_LEAF_SPHERE) {
-            geo[ord] = make_float4(L.f[0], L.f[1], L.f[2], L.f[3]);
-            kind[ord] = 1u;
-        }
-        pc_of[ord] = pc;
-        if (!terms.empty()) {  // boxes per term below
-            pc += 1u + r.u0;
-            continue;
-        }
-        LbPrim p;
-        p.ord = ord;
-        if (prim_aabb(prog, pc, p.lo, p.hi)) {
-            for (int a = 0; a < 3; ++a) {
-                const double m = 1e-4 * (fabs(p.lo[a]) + fabs(p.hi[a]) + (p.hi[a] - p.lo[a])) + 1e-5;
-                p.lo[a] -= m;
-                p.hi[a] += m;
-                p.c[a] = 0.5 * (p.lo[a] + p.hi[a]);
-            }
-            prims.push_back(p);
-        } else {
-            always.push_back(ord);
-        }
-        pc += 1u + r.u0;
-    }
-    // term mode: a term's box is the meet of its positive literals' boxes (its
-    // value, and every change of it, lies inside each of them); a term with no
-    // bounded positive literal goes to the always list
-    std::vector<float4> term_recs;
-    auto bits_f = [](uint32_t u) {
-        float f;
-        memcpy(&f, &u, sizeof f);
-        return f;
-    };
-    for (uint32_t ti = 0; ti < (uint32_t)terms.size(); ++ti) {
-        const auto& t = terms[ti];
-        // inline geometry: a literal that is one sphere, or two sphere members
-        float4 rec[kTermRecF4];
-        for (uint32_t k = 0; k < kTermRecF4; ++k) rec[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        uint32_t kinds = 0;
-        for (uint32_t x = 0; x < (uint32_t)t.size(); ++x) {
-            const uint32_t pc = pc_of[t[x] & ~kLitNeg];
-            const uint32_t nm = prog[pc].u0;
-            bool spheres = nm >= 1u && nm <= 2u;
-            for (uint32_t m = 0; m < nm && spheres; ++m) spheres = prog[pc + 1u + m].op == WO_LEAF_SPHERE;
-            if (!spheres) continue;
-            kinds |= (nm == 1u ? kTermLitSphere : kTermLitSphere2) << (2u * x);
-            for (uint32_t m = 0; m < 2u; ++m) {  // a single sphere repeats as member 1 (a no-op meet)
-                const WoRec& L = prog[pc + 1u + (m < nm ? m : 0u)];
-                rec[1u + 2u * x + m] = make_float4(L.f[0], L.f[1], L.f[2], L.f[3]);
-            }
-        }
-        if (t.size() == 1u) kinds |= kTermLitSphere << 2u;  // no second literal: a dummy sphere, masked out
-        rec[0] = make_float4(bits_f(t[0]), bits_f(t.size() > 1u ? t[1] : kNoLit), bits_f(kinds), 0.0f);
-        term_recs.insert(term_recs.end(), rec, rec + kTermRecF4);
-        LbPrim p;
-        p.ord = ti;
-        bool bounded = false;
-        for (int a = 0; a < 3; ++a) {
-            p.lo[a] = -INFINITY;
-            p.hi[a] = INFINITY;
-        }
-        for (uint32_t l : t) {
-            if (l & kLitNeg) continue;
-            double lo[3], hi[3];
-            if (!prim_aabb(prog, pc_of[l], lo, hi)) continue;
-            bounded = true;
-            for (int a = 0; a < 3; ++a) {
-                p.lo[a] = fmax(p.lo[a], lo[a]);
-                p.hi[a] = fmin(p.hi[a], hi[a]);
-            }
-        }
-        for (int a = 0; a < 3 && bounded; ++a)
-            if (p.lo[a] > p.hi[a]) p.hi[a] = p.lo[a];  // an empty meet: a point box (never empty arithmetic)
-        if (!bounded) {
-            always.push_back(ti);
-            continue;
-        }
-        for (int a = 0; a < 3; ++a) {
-            const double m = 1e-4 * (fabs(p.lo[a]) + fabs(p.hi[a]) + (p.hi[a] - p.lo[a])) + 1e-5;
-            p.lo[a] -= m;
-            p.hi[a] += m;
-            p.c[a] = 0.5 * (p.lo[a] + p.hi[a]);
-        }
-        prims.push_back(p);
-    }
-    // General tree: each primitive's relevance box, the meet of the bounds of the
-    // operands that gate it -- an intersection's other operand, a difference's
-    // left one for its right one -- along its path to the root (outside it the
-    // primitive cannot change the root).  The walk's leaf box becomes the meet of
-    // the primitive's box with it (twice the slack, so the clip's ends lie inside
-    // with room), a primitive whose meet is empty even with the slack never matters
-    // and leaves the walk, and an unbounded primitive with a bounded relevance box
-    // joins the BVH.  visit_leaf clips the primitive's interval to the box's span.
-    std::vector<float4> gclip;
-    if (dev->lb_general) {
-        typedef std::array<double, 6> Box;  // lo xyz, hi xyz
-        const Box inf_box = {-INFINITY, -INFINITY, -INFINITY, INFINITY, INFINITY, INFINITY};
-        auto meet = [](const Box& x, const Box& y) {
-            Box m;
-            for (int a = 0; a < 3; ++a) {
-                m[a] = fmax(x[a], y[a]);
-                m[3 + a] = fmin(x[3 + a], y[3 + a]);
-            }
-            return m;
-        };
-        auto hull = [](const Box& x, const Box& y) {
-            Box h;
-            for (int a = 0; a < 3; ++a) {
-                h[a] = fmin(x[a], y[a]);
-                h[3 + a] = fmax(x[3 + a], y[3 + a]);
-            }
-            return h;
-        };
-        auto slacked = [](Box x, double k) {
-            for (int a = 0; a < 3; ++a) {
-                if (!std::isfinite(x[a]) || !std::isfinite(x[3 + a])) continue;
-                const double m = k * (1e-4 * (fabs(x[a]) + fabs(x[3 + a]) + fabs(x[3 + a] - x[a])) + 1e-5);
-                x[a] -= m;
-                x[3 + a] += m;
-            }
-            return x;
-        };
-        const uint32_t nref = (uint32_t)gpar.size();
-        std::vector<Box> bnd(nref, inf_box), con(nref, inf_box);
-        for (uint32_t ord = 0; ord < n_prims; ++ord) {
-            double lo[3], hi[3];
-            if (prim_aabb(prog, pc_of[ord], lo, hi)) bnd[ord] = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
-        }
-        for (uint32_t i = 0; i < (uint32_t)gnode.size(); ++i) {  // operands before their node
-            const uint32_t nd = gnode[i], a = nd & kGRefMask, b = (nd >> kGRefBits) & kGRefMask, op = nd >> 30;
-            bnd[n_prims + i] = op == 0u ? hull(bnd[a], bnd[b]) : op == 1u ? meet(bnd[a], bnd[b]) : op == 2u ? bnd[a] : bnd[b];
-        }
-        for (uint32_t i = (uint32_t)gnode.size(); i-- > 0;) {  // a node before its operands
-            const uint32_t nd = gnode[i], a = nd & kGRefMask, b = (nd >> kGRefBits) & kGRefMask, op = nd >> 30;
-            const Box& c = con[n_prims + i];
-            con[a] = op == 1u ? meet(c, bnd[b]) : op == 3u ? meet(c, bnd[b]) : c;  // b AND NOT a: a gated by b
-            con[b] = op == 1u || op == 2u ? meet(c, bnd[a]) : c;                    // a AND NOT b: b gated by a
-        }
-        gclip.assign(2u * n_prims, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        std::vector<LbPrim> kept;
-        std::vector<uint32_t> alw;
-        size_t clipped = 0, dropped = 0;
-        for (uint32_t ord = 0; ord < n_prims; ++ord) {
-            const Box& c = con[ord];
-            bool bounded = false;
-            for (int a = 0; a < 6; ++a) bounded = bounded || std::isfinite(c[a]);
-            if (bounded) {
-                const Box cs = slacked(c, 1.0);
-                auto fl = [](double v) { return (float)fmax(-1e30, fmin(1e30, v)); };
-                gclip[2u * ord] = make_float4(fl(cs[0]), fl(cs[1]), fl(cs[2]), 1.0f);  // w != 0: clip
-                gclip[2u * ord + 1u] = make_float4(fl(cs[3]), fl(cs[4]), fl(cs[5]), 0.0f);
-                ++clipped;
-            }
-            const Box m = meet(slacked(bnd[ord], 2.0), slacked(c, 2.0));
-            bool empty = false, finite = true;
-            for (int a = 0; a < 3; ++a) {
-                empty = empty || m[a] > m[3 + a];
-                finite = finite && std::isfinite(m[a]) && std::isfinite(m[3 + a]);
-            }
-            if (empty) {
-                ++dropped;
-                continue;  // never matters: its bit stays 0
-            }
-            if (!finite) {
-                alw.push_back(ord);
-                continue;
-            }
-            LbPrim p;
-            p.ord = ord;
-            for (int a = 0; a < 3; ++a) {
-                p.lo[a] = m[a];
-                p.hi[a] = m[3 + a];
-                p.c[a] = 0.5 * (p.lo[a] + p.hi[a]);
-            }
-            kept.push_back(p);
-        }
-        prims.swap(kept);
-        always.swap(alw);
-        if (!clipped) gclip.clear();
-        (void)dropped;
-    }
-    if (!prims.empty()) {
-        std::vector<double> diag(prims.size());
-        for (size_t i = 0; i < prims.size(); ++i) {
-            double s = 0.0;
-            for (int a = 0; a < 3; ++a) s += (prims[i].hi[a] - prims[i].lo[a]) * (prims[i].hi[a] - prims[i].lo[a]);
-            diag[i] = sqrt(s);
-        }
-        std::vector<double> sorted = diag;
-        std::nth_element(sorted.begin(), sorted.begin() + sorted.size() / 2, sorted.end());
-        const double med = sorted[sorted.size() / 2];
-        std::vector<LbPrim> kept;
-        for (size_t i = 0; i < prims.size(); ++i) {
-            if (prims.size() > 4u && diag[i] > 16.0 * med)
-                always.push_back(prims[i].ord);
-            else
-                kept.push_back(prims[i]);
-        }
-        prims.swap(kept);
-    }
-    std::vector<float4> nodes;
-    if (ceil_log2((uint32_t)prims.size()) > kLaneDepthMax) {  // > 2^24 primitives (launches allow 2^20)
-        snprintf(err, errlen, "too many primitives for the lane BVH");
-        return -1;
-    }
-    if (!prims.empty()) {
-        // levels: SAH's freedom over the balanced tree's log2(n), within the stack's limit
-        // (the balanced tree, levels = log2(n): RTIOW cover 12.20 ms against 11.60)
-        uint32_t levels = ceil_log2((uint32_t)prims.size()) + 6u;
-        if (levels > kLaneDepthMax) levels = kLaneDepthMax;
-        LbBox root_box;
-        dev->lb_root = lb_build(prims, 0u, (uint32_t)prims.size(), levels, nodes, root_box, dev->lb_depth);
-        // 4-wide nodes: refs must fit the 16-bit stack entries.  For term mode over 256
-        // terms (csg512_balanced, resumable walks: 50.1 -> 44.7 ms over the binary tree;
-        // non-resumable 82.0 -> 70.5); neutral on csg256 balanced's 65 terms, 16.4 / 16.5
-        // ms; slower on csg32's 14, 8.9 -> 9.6, and on the RTIOW cover's spheres, 11.7 ->
-        // 13.7
-        const bool want_wide = terms.size() > 256u;
-        const uint32_t nrefs = terms.empty() ? n_prims : (uint32_t)terms.size();
-        if (want_wide && !(dev->lb_root & kLeafRef) && nrefs < 0x8000u) {
-            std::vector<float4> n4;
-            uint32_t lv4 = 0;
-            const uint32_t r4 = lb_collapse4(nodes, dev->lb_root, n4, lv4);
-            if (n4.size() / 7u < 0x8000u) {
-                lb_bfs4(n4, r4);
-                nodes.swap(n4);
-                dev->lb_root = 0u;
-                dev->lb_wide = true;
-                dev->lb_depth = 3u * lv4;  // stack entries: at most three siblings per level
-            }
-        }
-        // breadth-first node order: the top levels are then nodes [0, k), the ones
-        // every walk visits first, and they are staged in LDS (lb_top)
-        if (!dev->lb_wide && !(dev->lb_root & kLeafRef)) {
-            const uint32_t nn = (uint32_t)(nodes.size() / 4u);
-            auto ref_at = [&](uint32_t n, int c) {
-                uint32_t u;
-                memcpy(&u, &nodes[4u * n + (uint32_t)c].w, sizeof u);
-                return u;
-            };
-            std::vector<uint32_t> order, newidx(nn, 0u);
-            order.reserve(nn);
-            order.push_back(dev->lb_root);
-            for (size_t h = 0; h < order.size(); ++h)
-                for (int c = 0; c < 2; ++c) {
-                    const uint32_t r = ref_at(order[h], c);
-                    if (!(r & kLeafRef)) order.push_back(r);
-                }
-            for (uint32_t i = 0; i < nn; ++i) newidx[order[i]] = i;
-            std::vector<float4> bfs(nodes.size());
-            for (uint32_t i = 0; i < nn; ++i) {
-                for (int k = 0; k < 4; ++k) bfs[4u * i + (uint32_t)k] = nodes[4u * order[i] + (uint32_t)k];
-                for (int c = 0; c < 2; ++c) {
-                    uint32_t r = ref_at(order[i], c);
-                    if (!(r & kLeafRef)) r = newidx[r];
-                    memcpy(&bfs[4u * i + (uint32_t)c].w, &r, sizeof r);
-                }
-            }
-            nodes.swap(bfs);
-            dev->lb_root = 0u;
-        }
-    }
-    const uint32_t node_f4 = lb_node_f4(dev);
-    dev->lb_nodes = (uint32_t)(nodes.size() / node_f4);
-    dev->lb_always = (uint32_t)always.size();
-    {
-        // 16-bit stack entries for 4-wide nodes and the general tree (its bits need the
-        // LDS; binary trees otherwise: 32-bit, RTIOW cover 11.60 ms against 11.76 with
-        // 16-bit entries and more top nodes)
-        dev->lb_stack16 = dev->lb_wide || dev->lb_general;
-        if (dev->lb_general && (dev->lb_nodes >= 0x8000u || n_prims >= 0x8000u)) {
-            dev->lb_general = false;  // refs beyond the 16-bit stack entries: no lane form
-            return 0;
-        }
-        // the top nodes fill what the stacks leave of kLanesBvhLds (8 workgroups per CU)
-        const size_t stacks =
-            ((((size_t)dev->lb_depth * kBlock * (dev->lb_stack16 ? 2u : 4u)) + 15u) & ~(size_t)15u);
-        const size_t used = stacks + (dev->lb_general ? (size_t)((gpar.size() + 31u) / 32u) * kBlock * 4u : 0u);
-        // (the kernels with camera-ray waves give the ring's LDS: LaneTracer::kCamMode)
-        const size_t budget = kLanesBvhLds - (dev->lb_wide || dev->lb_general ? 0u : kCamRingLds);
-        const uint32_t top = used < budget ? (uint32_t)((budget - used) / (node_f4 * sizeof(float4))) : 0u;
-        dev->lb_top = top < dev->lb_nodes ? top : dev->lb_nodes;
-    }
-    dev->lb_spheres_only = terms.empty() && !dev->lb_general &&
-                           std::all_of(kind.begin(), kind.end(), [](uint32_t k) { return k != 0u; });
-    dev->lb_terms = (uint32_t)terms.size();
-    const size_t f4 = nodes.size() + n_prims;
-    // ... | kind per ordinal | always list | (term mode) kTermRecF4 float4 per term, 16-byte aligned
-    size_t words = (size_t)n_prims + always.size();
-    words = (words + 3u) & ~(size_t)3u;
-    const size_t term_off = f4 * sizeof(float4) + words * sizeof(uint32_t);
-    dev->lb_term_off = (uint32_t)(term_off / sizeof(uint32_t));
-    // single-sphere scenes: each ordinal's leaf record and its material (2 x 32 B), so
-    // a hit's shading reads them in two independent loads instead of the ordinal ->
-    // pc -> record -> material chain (hit_leaf, hit_material)
-    static_assert(sizeof(WoRec) == 32 && sizeof(WoMaterial) == 32, "leaf table entries are 2 x 32 bytes");
-    const size_t leaf_off = term_off + term_recs.size() * sizeof(float4);
-    dev->lb_leaf_off = dev->lb_spheres_only ? (uint32_t)(leaf_off / sizeof(uint32_t)) : 0u;
-    const size_t gpar_off = leaf_off + (dev->lb_spheres_only ? (size_t)n_prims * 2u * sizeof(WoRec) : 0u);
-    const size_t gnode_off = gpar_off + gpar.size() * sizeof(uint32_t);
-    const size_t gclip_off = (gnode_off + gnode.size() * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-    const size_t bytes = gclip_off + gclip.size() * sizeof(float4);
-    dev->lb_gpar_off = (uint32_t)(gpar_off / sizeof(uint32_t));
-    dev->lb_gnode_off = (uint32_t)(gnode_off / sizeof(uint32_t));
-    dev->lb_gclip_off = gclip.empty() ? 0u : (uint32_t)(gclip_off / sizeof(uint32_t));
-    dev->lb_gP = n_prims;
-    dev->lb_gwords = (uint32_t)((gpar.size() + 31u) / 32u);
-    dev->lb_groot = groot;
-    if (ensure_buffer(&dev->d_lbvh, &dev->lbvh_cap, bytes, err, errlen)) return -1;
-    std::vector<char> blob(bytes);
-    if (!gpar.empty()) memcpy(blob.data() + gpar_off, gpar.data(), gpar.size() * sizeof(uint32_t));
-    if (!gnode.empty()) memcpy(blob.data() + gnode_off, gnode.data(), gnode.size() * sizeof(uint32_t));
-    if (!gclip.empty()) memcpy(blob.data() + gclip_off, gclip.data(), gclip.size() * sizeof(float4));
-    if (dev->lb_spheres_only)
-        for (uint32_t ord = 0; ord < n_prims; ++ord) {
-            const WoRec& L = prog[pc_of[ord] + 1u];
-            char* e = blob.data() + leaf_off + (size_t)ord * 2u * sizeof(WoRec);
-            memcpy(e, &L, sizeof(WoRec));
-            if (L.u0 < n_mats) memcpy(e + sizeof(WoRec), &mats[L.u0], sizeof(WoMaterial));
-        }
-    memcpy(blob.data(), nodes.data(), nodes.size() * sizeof(float4));
-    memcpy(blob.data() + nodes.size() * sizeof(float4), geo.data(), n_prims * sizeof(float4));
-    memcpy(blob.data() + f4 * sizeof(float4), kind.data(), n_prims * sizeof(uint32_t));
-    memcpy(blob.data() + f4 * sizeof(float4) + n_prims * sizeof(uint32_t), always.data(),
-           always.size() * sizeof(uint32_t));
-    if (!term_recs.empty()) memcpy(blob.data() + term_off, term_recs.data(), term_recs.size() * sizeof(float4));
-    hipError_t e = hipMemcpy(dev->d_lbvh, blob.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_err(err, errlen, "hipMemcpy(lane BVH)", e);
-        return -1;
-    }
-    return 0;
-}
-
+// The kernels' view of the lane BVH (built on the host, lane_bvh_build.cpp): the
+// blob's sections through the descriptor's offsets.
 static LaneBvh lane_bvh(const WoDev* dev) {
+    const WoLaneBvhDesc& d = dev->lbvh;
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(dev->d_lbvh);
     LaneBvh b;
-    const uint32_t node_f4 = lb_node_f4(dev);
     b.nodes = dev->d_lbvh;
-    b.geo = dev->d_lbvh + node_f4 * dev->lb_nodes;
-    b.kind = reinterpret_cast<const uint32_t*>(dev->d_lbvh + node_f4 * dev->lb_nodes + dev->lb_nprims);
-    b.nalways = dev->lb_always;
-    b.root = dev->lb_root;
-    b.nprims = dev->lb_nprims;
-    b.ntop = dev->lb_top;
-    b.depth = dev->lb_depth;
+    b.geo = dev->d_lbvh + lane_node_f4(d) * d.nodes;
+    b.kind = reinterpret_cast<const uint32_t*>(b.geo + d.nprims);
+    b.nalways = d.always;
+    b.root = d.root;
+    b.nprims = d.nprims;
+    b.ntop = d.top;
+    b.depth = d.depth;
     // csg512_balanced: 60.4 / 57.6 / 57.2 / 58.1 / 59.2 ms at 8 / 16 / 24 / 32 / 40;
     // WOLOLO_DYN_WALKERS (measurement) overrides
     static const uint32_t walkers = [] {
@@ -2580,21 +1776,26 @@ static LaneBvh lane_bvh(const WoDev* dev) {
         return w && *w ? (uint32_t)atoi(w) : 24u;
     }();
     b.dyn_walkers = walkers;
-    b.trec = dev->lb_terms ? reinterpret_cast<const float4*>(reinterpret_cast<const uint32_t*>(dev->d_lbvh) +
-                                                            dev->lb_term_off)
-                           : nullptr;
-    b.leaves = dev->lb_leaf_off ? reinterpret_cast<const WoRec*>(reinterpret_cast<const uint32_t*>(dev->d_lbvh) +
-                                                                dev->lb_leaf_off)
-                                : nullptr;
-    b.gpar = reinterpret_cast<const uint32_t*>(dev->d_lbvh) + dev->lb_gpar_off;
-    b.gnode = reinterpret_cast<const uint32_t*>(dev->d_lbvh) + dev->lb_gnode_off;
-    b.gclip = dev->lb_gclip_off ? reinterpret_cast<const float4*>(reinterpret_cast<const uint32_t*>(dev->d_lbvh) +
-                                                                 dev->lb_gclip_off)
-                                : nullptr;
-    b.gP = dev->lb_gP;
-    b.gwords = dev->lb_gwords;
-    b.groot = dev->lb_groot;
+    b.trec = d.terms ? reinterpret_cast<const float4*>(words + d.term_off) : nullptr;
+    b.leaves = d.leaf_off ? reinterpret_cast<const WoRec*>(words + d.leaf_off) : nullptr;
+    b.gpar = words + d.gpar_off;
+    b.gnode = words + d.gnode_off;
+    b.gclip = d.gclip_off ? reinterpret_cast<const float4*>(words + d.gclip_off) : nullptr;
+    b.gP = d.gP;
+    b.gwords = d.gwords;
+    b.groot = d.groot;
     return b;
+}
+
+template <class T>
+static int upload(T** p, size_t* cap, const void* src, size_t bytes, const char* what, char* err, size_t errlen) {
+    if (ensure_buffer(p, cap, bytes, err, errlen)) return -1;
+    const hipError_t e = bytes ? hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) {
+        set_err(err, errlen, what, e);
+        return -1;
+    }
+    return 0;
 }
 
 extern "C" int wo_dev_upload_scene(WoDev* dev, WoRec const* prog, uint32_t n_recs, uint32_t n_prims,
@@ -2613,28 +1814,25 @@ extern "C" int wo_dev_upload_scene(WoDev* dev, WoRec const* prog, uint32_t n_rec
         set_err(err, errlen, "hipDeviceSynchronize (before scene upload)", e);
         return -1;
     }
-    if (ensure_buffer(&dev->d_prog, &dev->prog_cap, (size_t)n_recs * sizeof(WoRec), err, errlen)) return -1;
-    if (ensure_buffer(&dev->d_mats, &dev->mats_cap, (size_t)n_mats * sizeof(WoMaterial), err, errlen)) return -1;
-    if (n_recs) {
-        e = hipMemcpy(dev->d_prog, prog, (size_t)n_recs * sizeof(WoRec), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            set_err(err, errlen, "hipMemcpy(program)", e);
-            return -1;
-        }
-    }
-    if (n_mats) {
-        e = hipMemcpy(dev->d_mats, mats, (size_t)n_mats * sizeof(WoMaterial), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            set_err(err, errlen, "hipMemcpy(materials)", e);
-            return -1;
-        }
-    }
+    if (upload(&dev->d_prog, &dev->prog_cap, prog, (size_t)n_recs * sizeof(WoRec), "hipMemcpy(program)", err, errlen))
+        return -1;
+    if (upload(&dev->d_mats, &dev->mats_cap, mats, (size_t)n_mats * sizeof(WoMaterial), "hipMemcpy(materials)", err,
+               errlen))
+        return -1;
     dev->n_recs = n_recs;
     dev->n_prims = n_prims;
     dev->n_mats = n_mats;
     dev->n_nodes = ~0u;  // the node table is the previous scene's until wo_dev_upload_nodes
-    if (scene_maps(dev, prog, n_recs, n_prims, err, errlen)) return -1;
-    return build_lbvh(dev, prog, n_recs, n_prims, mats, n_mats, err, errlen);
+    LaneBvhBuild lb;
+    if (lane_bvh_build(prog, n_recs, n_prims, mats, n_mats, &lb, err, errlen)) return -1;
+    dev->lbvh = lb.desc;
+    if (upload(&dev->d_ordpc, &dev->ordpc_cap, lb.ordpc.data(), lb.ordpc.size() * sizeof(uint32_t),
+               "hipMemcpy(ordinal map)", err, errlen))
+        return -1;
+    // (no lane form: no blob, and no kernel that reads d_lbvh is launched)
+    return lb.blob.empty() ? 0
+                           : upload(&dev->d_lbvh, &dev->lbvh_cap, lb.blob.data(), lb.blob.size(), "hipMemcpy(lane BVH)",
+                                    err, errlen);
 }
 
 // ---- scene-specialised kernels (hiprtc) ----
@@ -3091,10 +2289,10 @@ extern "C" int wo_dev_jit_origin(WoDev* dev, double* seconds) {
 
 extern "C" int wo_dev_lanes_info(WoDev* dev, uint32_t* out) {
     if (!dev) return -1;
-    out[0] = dev->lb_nodes;
-    out[1] = dev->lb_depth;
-    out[2] = dev->lb_top;
-    out[3] = dev->lb_always;
+    out[0] = dev->lbvh.nodes;
+    out[1] = dev->lbvh.depth;
+    out[2] = dev->lbvh.top;
+    out[3] = dev->lbvh.always;
     out[4] = dev->ray_last ? dev->ray_kind : dev->last_kind;
     return 0;
 }
@@ -3105,9 +2303,8 @@ extern "C" int wo_jit_compile_check(const char* src, const char* arch, char* err
 }
 
 extern "C" int wo_dev_jit_active(WoDev* dev) { return dev && dev->jit_fn ? 1 : 0; }
-extern "C" int wo_dev_lanes_available(WoDev* dev) {
-    return dev && (dev->union_only || dev->lb_terms || dev->lb_general) ? 1 : 0;
-}
+static bool has_lane_form(const WoLaneBvhDesc& d) { return d.union_only || d.terms || d.general; }
+extern "C" int wo_dev_lanes_available(WoDev* dev) { return dev && has_lane_form(dev->lbvh) ? 1 : 0; }
 extern "C" void wo_dev_set_lanes(WoDev* dev, int on) {
     if (dev) dev->lanes_on = on != 0;
 }
@@ -3202,7 +2399,6 @@ static PathLaunch plan_tiles(uint32_t width, uint32_t rows, uint32_t resident, u
 }
 
 static const size_t kLdsBudget = 64u * 1024u;
-// Lane-traversal nodes in LDS: up to ~1200 nodes keeps 6 workgroups per CU
 
 extern "C" int wo_dev_launch(WoDev* dev, WoFrame const* frame_in, void* d_out, void* stream_v,
                              unsigned long long* d_segments, char* err, size_t errlen) {
@@ -3213,40 +2409,38 @@ extern "C" int wo_dev_launch(WoDev* dev, WoFrame const* frame_in, void* d_out, v
 enum PathKind { kLanesBvh = 2, kLanesBvhSpheres = 3, kLanesTerms = 6, kLanesGeneral = 7, kLanesDynWideTerms = 14,
                 kJit = 16, kInterpLds = 17, kInterpGlobal = 18 };
 
+// The library's kernel of a kind (`count`: its counting variant) for the pointer
+// forms of the occupancy, attribute and launch calls; nullptr for kJit, whose
+// kernel is the device's loaded module.  The lane kernels take lane_args' list,
+// the interpreter's interp_args'.
 template <bool kCount>
-static hipError_t static_occupancy(PathKind kind, size_t dyn_lds, int* per_cu) {
+static const void* path_kernel_of(PathKind kind) {
     switch (kind) {
-    case kLanesBvh:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pathtrace_lanes_kernel<2, kCount>, kBlock, dyn_lds);
-    case kLanesBvhSpheres:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pathtrace_lanes_kernel<3, kCount>, kBlock, dyn_lds);
-    case kLanesTerms:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pathtrace_lanes_kernel<6, kCount>, kBlock, dyn_lds);
-    case kLanesGeneral:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pathtrace_lanes_kernel<7, kCount>, kBlock, dyn_lds);
-    case kLanesDynWideTerms:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pathtrace_lanes_kernel<14, kCount>, kBlock, dyn_lds);
-    case kInterpLds:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pathtrace_kernel<true, kCount>, kBlock, dyn_lds);
-    default:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, pathtrace_kernel<false, kCount>, kBlock, dyn_lds);
+    case kLanesBvh: return (const void*)pathtrace_lanes_kernel<2, kCount>;
+    case kLanesBvhSpheres: return (const void*)pathtrace_lanes_kernel<3, kCount>;
+    case kLanesTerms: return (const void*)pathtrace_lanes_kernel<6, kCount>;
+    case kLanesGeneral: return (const void*)pathtrace_lanes_kernel<7, kCount>;
+    case kLanesDynWideTerms: return (const void*)pathtrace_lanes_kernel<14, kCount>;
+    case kInterpLds: return (const void*)pathtrace_kernel<true, kCount>;
+    case kInterpGlobal: return (const void*)pathtrace_kernel<false, kCount>;
+    case kJit: break;
+    }
+    return nullptr;
+}
+static const void* path_kernel(PathKind kind, bool count) {
+    return !count ? path_kernel_of<false>(kind) : path_kernel_of<true>(kind);
+}
+// the same for a ray launch's four kernels
+static const void* ray_kernel(PathKind kind) {
+    switch (kind) {
+    case kLanesBvh: return (const void*)trace_rays_lanes_kernel<2>;
+    case kLanesBvhSpheres: return (const void*)trace_rays_lanes_kernel<3>;
+    case kInterpLds: return (const void*)trace_rays_kernel<true>;
+    case kInterpGlobal: return (const void*)trace_rays_kernel<false>;
+    default: return nullptr;
     }
 }
-
-// Resources of one path kernel as the runtime loaded it (hipFuncGetAttributes):
-// private (scratch) bytes per lane, VGPRs, static LDS.
-template <bool kCount>
-static hipError_t static_attrs(PathKind kind, hipFuncAttributes* a) {
-    switch (kind) {
-    case kLanesBvh: return hipFuncGetAttributes(a, (const void*)pathtrace_lanes_kernel<2, kCount>);
-    case kLanesBvhSpheres: return hipFuncGetAttributes(a, (const void*)pathtrace_lanes_kernel<3, kCount>);
-    case kLanesTerms: return hipFuncGetAttributes(a, (const void*)pathtrace_lanes_kernel<6, kCount>);
-    case kLanesGeneral: return hipFuncGetAttributes(a, (const void*)pathtrace_lanes_kernel<7, kCount>);
-    case kLanesDynWideTerms: return hipFuncGetAttributes(a, (const void*)pathtrace_lanes_kernel<14, kCount>);
-    case kInterpLds: return hipFuncGetAttributes(a, (const void*)pathtrace_kernel<true, kCount>);
-    default: return hipFuncGetAttributes(a, (const void*)pathtrace_kernel<false, kCount>);
-    }
-}
+static bool is_lane_kind(PathKind kind) { return kind < kJit; }
 
 // The path kernel of the last launch: key_hex (65 bytes) gets the specialised
 // kernel's code-object key (jit_key) or "static:<kind>:<source hash>"; out[0] = kind (PathKind),
@@ -3267,51 +2461,13 @@ extern "C" int wo_dev_kernel_info(WoDev* dev, char* key_hex, uint32_t* out) {
     } else {
         // "static:<kind>:" + the first 40 hex digits of the library kernels' source hash
         hipFuncAttributes a;
-        if (static_attrs<false>(kind, &a) != hipSuccess) return -1;
+        if (hipFuncGetAttributes(&a, path_kernel(kind, false)) != hipSuccess) return -1;
         out[1] = (uint32_t)a.localSizeBytes;
         out[2] = (uint32_t)a.numRegs;
         out[3] = (uint32_t)a.sharedSizeBytes;
         if (key_hex) snprintf(key_hex, 65, "static:%u:%.40s", (unsigned)kind, WO_STATIC_SRC_SHA);
     }
     return 0;
-}
-
-template <int kMode, bool kCount>
-static void lanes_launch(dim3 grid, size_t dyn_lds, hipStream_t stream, WoDev* dev, const WoFrame& fr,
-                         uint32_t local_rows, float4* out, unsigned long long* slots, const PathLaunch& tg) {
-    hipLaunchKernelGGL((pathtrace_lanes_kernel<kMode, kCount>), grid, dim3(kBlock), dyn_lds, stream, dev->d_prog,
-                       dev->d_ordpc, dev->d_mats, fr, local_rows, out, slots, tg, lane_bvh(dev));
-}
-
-template <bool kCount>
-static void static_launch(PathKind kind, dim3 grid, size_t dyn_lds, hipStream_t stream, WoDev* dev, const WoFrame& fr,
-                          const KLayout& lay, uint32_t local_rows, float4* out, unsigned long long* slots,
-                          const PathLaunch& tg) {
-    switch (kind) {
-    case kLanesBvh:
-        lanes_launch<2, kCount>(grid, dyn_lds, stream, dev, fr, local_rows, out, slots, tg);
-        break;
-    case kLanesBvhSpheres:
-        lanes_launch<3, kCount>(grid, dyn_lds, stream, dev, fr, local_rows, out, slots, tg);
-        break;
-    case kLanesTerms:
-        lanes_launch<6, kCount>(grid, dyn_lds, stream, dev, fr, local_rows, out, slots, tg);
-        break;
-    case kLanesGeneral:
-        lanes_launch<7, kCount>(grid, dyn_lds, stream, dev, fr, local_rows, out, slots, tg);
-        break;
-    case kLanesDynWideTerms:
-        lanes_launch<14, kCount>(grid, dyn_lds, stream, dev, fr, local_rows, out, slots, tg);
-        break;
-    case kInterpLds:
-        hipLaunchKernelGGL((pathtrace_kernel<true, kCount>), grid, dim3(kBlock), dyn_lds, stream, dev->d_prog,
-                           dev->d_mats, fr, lay, local_rows, out, slots, tg);
-        break;
-    default:
-        hipLaunchKernelGGL((pathtrace_kernel<false, kCount>), grid, dim3(kBlock), dyn_lds, stream, dev->d_prog,
-                           dev->d_mats, fr, lay, local_rows, out, slots, tg);
-        break;
-    }
 }
 
 static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* stream_v,
@@ -3402,19 +2558,15 @@ static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* s
         PathKind kind;
         size_t dyn_lds = 0;
         KLayout lay = {};
-        if (dev->lanes_on && (dev->union_only || dev->lb_terms || dev->lb_general) && !dev->jit_fn) {
-            // the ordered BVH, its lane stacks and top nodes in LDS.  Term mode over more
-            // than 256 terms: the 4-wide tree with the resumable walk (dynamic ray fetch;
-            // csg512_balanced 84.3 -> 44.7 ms; slower where walks are short or alike: the
-            // RTIOW cover 11.7 -> 12.9-15.5 ms, csg256 balanced's 65 terms 16.5 -> 18.2;
-            // DESIGN.md §3.6c)
-            kind = dev->lb_wide      ? kLanesDynWideTerms
-                   : dev->lb_terms   ? kLanesTerms
-                   : dev->lb_general ? kLanesGeneral
-                   : (dev->lb_spheres_only ? kLanesBvhSpheres : kLanesBvh);
-            const size_t stacks = ((size_t)dev->lb_depth * kBlock * (dev->lb_stack16 ? 2u : 4u) + 15u) & ~(size_t)15u;
-            dyn_lds = stacks + (size_t)dev->lb_top * lb_node_f4(dev) * sizeof(float4);
-            if (dev->lb_general) dyn_lds += (size_t)dev->lb_gwords * kBlock * sizeof(uint32_t);  // the tree's bits
+        const WoLaneBvhDesc& lb = dev->lbvh;
+        if (dev->lanes_on && has_lane_form(lb) && !dev->jit_fn) {
+            // the ordered BVH, its lane stacks and top nodes in LDS; the 4-wide tree (term mode
+            // over more than 256 terms) runs the resumable walk
+            kind = lb.wide      ? kLanesDynWideTerms
+                   : lb.terms   ? kLanesTerms
+                   : lb.general ? kLanesGeneral
+                   : (lb.spheres_only ? kLanesBvhSpheres : kLanesBvh);
+            dyn_lds = lane_bvh_lds(lb);
         } else if (dev->jit_fn) {
             kind = kJit;
         } else if (interp_plan(fr.n_recs, fr.n_prims, &lay, &kind, &dyn_lds, err, errlen)) {
@@ -3427,7 +2579,7 @@ static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* s
         if (kind == kJit)
             e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, jfn, kBlock, 0);
         else
-            e = count ? static_occupancy<true>(kind, dyn_lds, &per_cu) : static_occupancy<false>(kind, dyn_lds, &per_cu);
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, path_kernel(kind, count), kBlock, dyn_lds);
         if (e != hipSuccess || per_cu < 1) per_cu = 1;
         // a rank's local rows are bands of tile_rows consecutive frame rows: a tile
         // taller than a band would join rows far apart (incoherent primary rays)
@@ -3459,10 +2611,13 @@ static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* s
                 set_err(err, errlen, "hipModuleLaunchKernel", e);
                 return -1;
             }
-        } else if (count) {
-            static_launch<true>(kind, grid, dyn_lds, stream, dev, fr, lay, local_rows, out, slots, tg);
         } else {
-            static_launch<false>(kind, grid, dyn_lds, stream, dev, fr, lay, local_rows, out, slots, tg);
+            LaneBvh bvh = lane_bvh(dev);
+            void* lane_args[] = {&dev->d_prog, &dev->d_ordpc, &dev->d_mats, &fr, &local_rows, &out, &slots, &tg, &bvh};
+            void* interp_args[] = {&dev->d_prog, &dev->d_mats, &fr, &lay, &local_rows, &out, &slots, &tg};
+            // (a failed launch is hipGetLastError's below)
+            (void)hipLaunchKernel(path_kernel(kind, count), grid, dim3(kBlock), is_lane_kind(kind) ? lane_args : interp_args,
+                                  dyn_lds, stream);
         }
         if (slots) hipLaunchKernelGGL(seg_collect_kernel, dim3(1), dim3(kBlock), 0, stream, slots, d_segments);
     } else {
@@ -3486,14 +2641,9 @@ extern "C" int wo_dev_upload_nodes(WoDev* dev, uint32_t const* nodes, uint32_t n
         return -1;
     }
     dev->n_nodes = ~0u;
-    if (ensure_buffer(&dev->d_nodes, &dev->nodes_cap, (size_t)n_recs * sizeof(uint32_t), err, errlen)) return -1;
-    if (n_recs) {
-        e = hipMemcpy(dev->d_nodes, nodes, (size_t)n_recs * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            set_err(err, errlen, "hipMemcpy(node table)", e);
-            return -1;
-        }
-    }
+    if (upload(&dev->d_nodes, &dev->nodes_cap, nodes, (size_t)n_recs * sizeof(uint32_t), "hipMemcpy(node table)", err,
+               errlen))
+        return -1;
     dev->n_nodes = n_recs;
     return 0;
 }
@@ -3543,40 +2693,26 @@ extern "C" int wo_dev_trace_rays(WoDev* dev, void const* d_rays, void* d_hits, s
     rb.n_mats = dev->n_mats;
     // the lane walk for a union-only scene (its BVH is built at every upload), unless
     // the interpreter is asked for; a scene that is not union-only has no plain walk
-    const bool lanes = form != 1 && dev->union_only && !dev->lb_terms && !dev->lb_general && !dev->lb_wide;
+    const WoLaneBvhDesc& lb = dev->lbvh;
+    const bool lanes = form != 1 && lb.union_only && !lb.stack16;  // (the ray kernels' stacks are 32-bit)
     PathKind kind;
     size_t dyn_lds = 0;
     KLayout lay = {};
-    int per_cu = 0;
     if (lanes) {
-        kind = dev->lb_spheres_only ? kLanesBvhSpheres : kLanesBvh;
-        const size_t stacks = ((size_t)dev->lb_depth * kBlock * 4u + 15u) & ~(size_t)15u;
-        dyn_lds = stacks + (size_t)dev->lb_top * 4u * sizeof(float4);
-        e = kind == kLanesBvh
-                ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_lanes_kernel<2>, kBlock, dyn_lds)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_lanes_kernel<3>, kBlock, dyn_lds);
-        if (e != hipSuccess || per_cu < 1) per_cu = 1;
-        const dim3 grid(ray_grid(dev, n, per_cu));
-        if (kind == kLanesBvh)
-            hipLaunchKernelGGL(trace_rays_lanes_kernel<2>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->d_ordpc,
-                               lane_bvh(dev), rb);
-        else
-            hipLaunchKernelGGL(trace_rays_lanes_kernel<3>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->d_ordpc,
-                               lane_bvh(dev), rb);
-    } else {
-        if (interp_plan(dev->n_recs, dev->n_prims, &lay, &kind, &dyn_lds, err, errlen)) return -1;
-        e = kind == kInterpLds
-                ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_kernel<true>, kBlock, dyn_lds)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_rays_kernel<false>, kBlock, dyn_lds);
-        if (e != hipSuccess || per_cu < 1) per_cu = 1;
-        const dim3 grid(ray_grid(dev, n, per_cu));
-        if (kind == kInterpLds)
-            hipLaunchKernelGGL(trace_rays_kernel<true>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->n_recs, lay,
-                               rb);
-        else
-            hipLaunchKernelGGL(trace_rays_kernel<false>, grid, dim3(kBlock), dyn_lds, stream, dev->d_prog, dev->n_recs,
-                               lay, rb);
+        kind = lb.spheres_only ? kLanesBvhSpheres : kLanesBvh;
+        dyn_lds = lane_bvh_lds(lb);
+    } else if (interp_plan(dev->n_recs, dev->n_prims, &lay, &kind, &dyn_lds, err, errlen)) {
+        return -1;
     }
+    const void* kernel = ray_kernel(kind);
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, dyn_lds);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    LaneBvh bvh = lane_bvh(dev);
+    void* lane_args[] = {&dev->d_prog, &dev->d_ordpc, &bvh, &rb};
+    void* interp_args[] = {&dev->d_prog, &dev->n_recs, &lay, &rb};
+    (void)hipLaunchKernel(kernel, dim3(ray_grid(dev, n, per_cu)), dim3(kBlock), lanes ? lane_args : interp_args, dyn_lds,
+                          stream);
     e = hipGetLastError();
     if (e != hipSuccess) {
         set_err(err, errlen, "ray kernel launch", e);

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "wololo/wo_scene.h"
+#include "lane_bvh.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -151,6 +152,13 @@ int wo_jit_disk_store(const char* key_hex, const void* code, size_t size);
  * device's specialised kernel was loaded from. */
 int wo_dev_jit_origin(WoDev* dev, double* seconds);
 int wo_dev_lanes_info(WoDev* dev, uint32_t* out);
+/* lane_bvh_build.cpp: the lane BVH of a compiled program as wo_dev_upload_scene builds
+ * it, without a device: its descriptor, *size = the packed blob's bytes (0: no lane
+ * form), copied to `blob` when they fit `cap`, and info = the dynamic LDS of a lane
+ * kernel's workgroup, the budget the builder keeps it within, a binary tree's most levels. */
+int wo_lane_bvh_build(WoRec const* prog, uint32_t n_recs, uint32_t n_prims, WoMaterial const* mats, uint32_t n_mats,
+                      WoLaneBvhDesc* desc, uint32_t info[3], void* blob, size_t cap, size_t* size, char* err,
+                      size_t errlen);
 /* the last launch's path kernel: key (65 B), out[4] = kind, scratch B/lane, VGPRs, LDS */
 int wo_dev_kernel_info(WoDev* dev, char* key_hex, uint32_t* out);
 /* Wait for the slot's frame; *host = its pixels (RGBA float; NULL when the

@@ -642,6 +642,32 @@ def jit_compile_check(src: str, arch: str = "gfx950") -> str:
     return "" if rc == 0 else err.value.decode(errors="replace")
 
 
+class LaneBvhDesc(Structure):
+    """Mirror of WoLaneBvhDesc (csrc/lane_bvh.h): all uint32."""
+    _fields_ = [(n, c_uint32) for n in (
+        "nprims", "nodes", "always", "root", "depth", "top", "terms", "union_only", "spheres_only", "stack16",
+        "wide", "general", "term_off", "leaf_off", "gpar_off", "gnode_off", "gclip_off", "gP", "gwords", "groot")]
+
+
+def lane_bvh(prog, n_recs: int, n_prims: int, mats, n_mats: int):
+    """The lane tracer's BVH of a compiled program, built on the host (csrc/wo_dev.h
+    wo_lane_bvh_build; no GPU needed): (descriptor, blob bytes, dynamic LDS bytes of a lane
+    kernel's workgroup, (the LDS budget, the most levels of a binary tree))."""
+    build = load().wo_lane_bvh_build
+    build.argtypes = [POINTER(WoRec), c_uint32, c_uint32, POINTER(WoMaterial), c_uint32, POINTER(LaneBvhDesc),
+                      POINTER(c_uint32), c_char_p, c_size_t, POINTER(c_size_t), c_char_p, c_size_t]
+    desc, info, size, blob = LaneBvhDesc(), (c_uint32 * 3)(), c_size_t(0), ctypes.create_string_buffer(0)
+    err = ctypes.create_string_buffer(256)
+    for _ in range(2):  # the size, then the bytes
+        if build(prog, n_recs, n_prims, mats, n_mats, ctypes.byref(desc), info, blob, len(blob), ctypes.byref(size),
+                 err, len(err)):
+            raise WololoError(err.value.decode(errors="replace"))
+        if size.value <= len(blob):
+            break
+        blob = ctypes.create_string_buffer(size.value)
+    return desc, blob.raw[:size.value], int(info[0]), (int(info[1]), int(info[2]))
+
+
 BAND_CYCLE_MAX = 65536  # wo_scene.h WO_BAND_CYCLE_MAX
 
 

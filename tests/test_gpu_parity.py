@@ -96,43 +96,6 @@ def _union_only(r):
     return nprim > 0
 
 
-def _union_of_terms(r, max_lits=2):
-    """Restatement of trace_kernels.hip extract_terms: the root is a union of terms, each
-    a conjunction of at most max_lits literals (a primitive or its complement), and
-    every primitive is in one term -- the lane tracer's term mode."""
-    prog, nrec, nprim = r.program()
-    st = []
-    pc = 0
-    while pc < nrec:
-        op = prog[pc].op
-        if op == wl.WO_OP_PRIM:
-            st.append(("conj", [(prog[pc].u1, True)]))
-            pc += 1 + prog[pc].u0
-            continue
-        pc += 1
-        if op == wl.WO_OP_BOUND:
-            continue
-        b, a = st.pop(), st.pop()
-        out = ("bad", None)
-        terms_of = lambda x: [x[1]] if x[0] == "conj" else x[1]
-        if a[0] != "bad" and b[0] != "bad":
-            if op == wl.WO_OP_UNION:
-                out = ("union", terms_of(a) + terms_of(b))
-            elif op == wl.WO_OP_INTER and a[0] == b[0] == "conj":
-                out = ("conj", a[1] + b[1])
-            elif op in (wl.WO_OP_DIFF, wl.WO_OP_RDIFF):
-                keep, sub = (a, b) if op == wl.WO_OP_DIFF else (b, a)
-                singles = terms_of(sub)
-                if keep[0] == "conj" and all(len(t) == 1 and t[0][1] for t in singles):
-                    out = ("conj", keep[1] + [(t[0][0], False) for t in singles])
-        st.append(out)
-    if len(st) != 1 or st[0][0] == "bad":
-        return False
-    terms = [st[0][1]] if st[0][0] == "conj" else st[0][1]
-    ords = [o for t in terms for o, _ in t]
-    return all(1 <= len(t) <= max_lits for t in terms) and len(ords) == len(set(ords))
-
-
 def _lanes_eligible(r):
     """The lane tracer takes every scene: union-only (a count), a union of small terms
     (term mode), else the general tree (its value kept per lane, kind 7)."""
