@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "wo_dev.h"
@@ -383,9 +384,10 @@ bool extract_terms(WoRec const* prog, uint32_t n_recs, uint32_t n_prims, Terms& 
         st.push_back(out);
     }
     if (st.size() != 1u || st[0].kind == 2) return false;
-    terms = as_terms(st[0]);
+    // (`terms` is written only on success: the caller builds term records from whatever it holds)
+    Terms got = as_terms(st[0]);
     std::vector<uint8_t> seen(n_prims, 0);
-    for (const auto& t : terms) {
+    for (const auto& t : got) {
         if (t.empty() || t.size() > kTermLits) return false;
         for (uint32_t l : t) {
             const uint32_t o = l & ~kLitNeg;
@@ -393,6 +395,7 @@ bool extract_terms(WoRec const* prog, uint32_t n_recs, uint32_t n_prims, Terms& 
             seen[o] = 1;
         }
     }
+    terms = std::move(got);
     return true;
 }
 

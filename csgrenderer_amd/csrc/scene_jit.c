@@ -122,6 +122,10 @@ typedef struct TEnt {
 static int bound_tested(const Gen* g, uint32_t pc) {
     const WoRec* r = &g->prog[pc];
     if (g->spatial) return 0; /* the spatial hierarchy culls instead (gen_spatial) */
+    /* ... or the relevance groups (gen_rtree): they number cull[]'s bits, and a set bit says
+     * "cannot change the root", not "false": the flat evaluation (WO_JIT_LUT=0) must not
+     * read them as its BOUND records' */
+    if (g->rtree) return 0;
     if (r->u1 < g->bound_min_leaves) return 0;
     if (pc + 1u < g->n && g->prog[pc + 1u].op == WO_OP_PRIM &&
         pc + 2u + g->prog[pc + 1u].u0 == r->u0)

@@ -97,16 +97,16 @@ class Scene:
         return exp
 
 
-def make_batch(r, scene, n=N_RAYS):
-    """The seeded batch of a scene (no device needed): (a) pixel rays of a coarse grid, (b)
-    origins uniform in the scene's box with uniform directions, (c) origins on the surface
-    (the oracle's hit points of (a)) with uniform directions, (d) axis-parallel directions."""
+def make_batch(r, scene, n=N_RAYS, nb=1500, step=3, box=None, seed=None):
+    """The seeded batch of a scene (no device needed): (a) pixel rays of a coarse grid (every
+    `step`-th pixel), (b) `nb` origins uniform in the scene's box with uniform directions, (c)
+    origins on the surface (the oracle's hit points of (a)) with uniform directions, (d)
+    axis-parallel directions.  `box` and `seed` stand in for a scene BOXES / SEEDS do not list."""
     sc = Scene(r)
-    rng = np.random.default_rng(SEEDS[scene])
-    lo, hi = (np.array(v, dtype=np.float64) for v in BOXES[scene])
+    rng = np.random.default_rng(SEEDS[scene] if seed is None else seed)
+    lo, hi = (np.array(v, dtype=np.float64) for v in (box or BOXES[scene]))
     p = wl.render_params(96, 54, mode=wl.MODE_NORMALS)
-    a = np.stack([r.pixel_ray(p, x, y) for y in range(1, 54, 3) for x in range(1, 96, 3)])
-    nb = 1500
+    a = np.stack([r.pixel_ray(p, x, y) for y in range(1, 54, step) for x in range(1, 96, step)])
     b = _rows(rng.uniform(lo, hi, size=(nb, 3)), _unit(rng.normal(size=(nb, 3))))
     ea = sc.expect(a)
     oc = rng.uniform(lo, hi, size=(len(a), 3)).astype(np.float32)

@@ -14,90 +14,7 @@ import pytest
 import pyoracle
 from csgrenderer_amd import scenes
 from csgrenderer_amd import wololo as wl
-
-
-class Shadow:
-    """Records nodes as they are added through the C API."""
-
-    def __init__(self, r: wl.Renderer):
-        self.r = r
-        self.nodes = []
-        self.nonroot = set()
-
-    def sphere(self, rad):
-        n = self.r.sphere(rad)
-        self.nodes.append(("s", rad))
-        return n
-
-    def halfspace(self, nrm):
-        n = self.r.halfspace(nrm)
-        self.nodes.append(("h", np.array(nrm, dtype=np.float64)))
-        return n
-
-    def binop(self, op, a, b):
-        fn = {"u": self.r.union, "i": self.r.intersection, "d": self.r.difference}[op]
-        n = fn(a, b)
-        self.nodes.append((op, a, b))
-        self.nonroot.update([a.node, b.node])
-        return n
-
-    # ---- float64 point classification ----
-    @staticmethod
-    def _to_local(arg, p):
-        q = arg.orientation
-        w, x, y, z = q.real, q.imaginary.x, q.imaginary.y, q.imaginary.z
-        nq = math.sqrt(w * w + x * x + y * y + z * z)
-        w, x, y, z = (1.0, 0.0, 0.0, 0.0) if nq == 0 else (w / nq, x / nq, y / nq, z / nq)
-        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                      [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-        off = np.array([arg.offset.x, arg.offset.y, arg.offset.z])
-        return R.T @ (p - off)
-
-    def inside(self, node, p):
-        nd = self.nodes[node]
-        if nd[0] == "s":
-            return float(np.dot(p, p)) <= abs(nd[1]) ** 2
-        if nd[0] == "h":
-            n = nd[1]
-            ln = np.linalg.norm(n)
-            return True if ln == 0 else float(np.dot(n / ln, p)) <= 0.0
-        a = self.inside(nd[1].node, self._to_local(nd[1], p))
-        b = self.inside(nd[2].node, self._to_local(nd[2], p))
-        return {"u": a or b, "i": a and b, "d": a and not b}[nd[0]]
-
-    def scene_inside(self, p):
-        return any(self.inside(i, p) for i in range(len(self.nodes)) if i not in self.nonroot)
-
-
-def _rand_quat(rng):
-    v = rng.normal(size=4)
-    v /= np.linalg.norm(v)
-    return wl.Quaternion(v[0], wl.Vec3(v[1], v[2], v[3]))
-
-
-def _random_scene(seed, n_leaves=10, axis=False):
-    """axis=True: half-space normals are +-e_a and operands are only translated, so
-    the compiled leaves are axis-aligned (u1 != 0) and take the reciprocal path."""
-    rng = np.random.default_rng(seed)
-    r = wl.Renderer(f"rand{seed}", max_nodes=256)
-    sh = Shadow(r)
-    pool = []
-    for _ in range(n_leaves):
-        if rng.random() < 0.7:
-            pool.append(sh.sphere(rng.uniform(0.4, 1.2)))
-        else:
-            nrm = np.eye(3)[rng.integers(3)] * rng.choice([-1.0, 1.0]) if axis else rng.normal(size=3)
-            pool.append(sh.halfspace(nrm))
-    while len(pool) > 1:
-        i, j = rng.choice(len(pool), 2, replace=False)
-        a, b = pool[i], pool[j]
-        op = rng.choice(["u", "i", "d"], p=[0.45, 0.3, 0.25])
-        mk = lambda n: wl.arg(n, tuple(rng.uniform(-1.0, 1.0, 3)),
-                              _rand_quat(rng) if rng.random() < 0.5 and not axis else None)
-        n = sh.binop(op, mk(a), mk(b))
-        pool = [x for k, x in enumerate(pool) if k not in (i, j)] + [n]
-    return r, sh, rng
+from gen_scenes import Shadow, _rand_quat, _random_scene  # noqa: F401  (the generators live there)
 
 
 def _program_checks(prog, nrec, nprim):
