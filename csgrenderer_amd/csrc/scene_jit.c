@@ -57,6 +57,13 @@ static void bput(Buf* b, const char* fmt, ...) {
     }
 }
 
+/* "every one of the n tile pre-cull entries is culled" over the words `arr`: a
+ * parenthesised comparison per word (the last word's mask has the table's tail bits) */
+static void put_all_culled(Buf* b, const char* arr, uint32_t n) {
+    for (uint32_t w = 0; w < (n + 31u) / 32u; ++w)
+        bput(b, "%s(%s[%u] == 0x%08xu)", w ? " & " : "", arr, w, n - 32u * w >= 32u ? 0xffffffffu : (1u << (n - 32u * w)) - 1u);
+}
+
 static uint32_t fbits(float v) {
     uint32_t u;
     memcpy(&u, &v, sizeof u);
@@ -2477,12 +2484,18 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
         bput(&b, "};\n");
     }
     bput(&b, "struct JitTracer {\n");
-    if (n_tile)
+    if (n_tile) {
         bput(&b,
              "  static constexpr uint32_t kTileCullEntries = %uu, kTileCullWords = %uu;\n"
              "  static __device__ __forceinline__ const wodev::TileBound& tile_bound(uint32_t e) { return kTileBound[e]; }\n"
              "  uint32_t pre[%u];  // the cull words the next trace starts from (pathtrace_block: the tile's, or 0)\n",
              n_tile, (n_tile + 31u) / 32u, (n_tile + 31u) / 32u);
+        /* whether a tile's words cull every entry: trace's early return below, and the
+         * block's choice of the sky loop for such a tile (pathtrace_block) */
+        bput(&b, "  static __device__ __forceinline__ bool tile_all_culled(const uint32_t* words) { return ");
+        put_all_culled(&b, "words", n_tile);
+        bput(&b, "; }\n");
+    }
     bput(&b,
          "  static constexpr bool kCount = WO_COUNT_WORK != 0;  // counting variant: -DWO_COUNT_WORK=1\n"
          "  wodev::WorkCounts wk;\n"
@@ -2513,8 +2526,7 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
         bput(&b, "    const float tmin = WO_T_MIN;\n");
         if (n_tile) { /* a tile none of whose rays can meet anything: no hit, before any arithmetic */
             bput(&b, "    if (");
-            for (uint32_t w = 0; w < (n_tile + 31u) / 32u; ++w)
-                bput(&b, "%s(pre[%u] == 0x%08xu)", w ? " & " : "", w, n_tile - 32u * w >= 32u ? 0xffffffffu : (1u << (n_tile - 32u * w)) - 1u);
+            put_all_culled(&b, "pre", n_tile);
             bput(&b, ") return false;\n");
         }
         /* reciprocal direction components for the axes axis-aligned half-spaces use */

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction mix of a scene's generated kernel per path-loop section (the
-WO_ISA_MARKS markers: cam_begin, collect_begin/end, shade_begin/end, take_begin), by
+WO_ISA_MARKS markers: cam_begin, collect_begin/end, shade_begin/end, take_begin, and
+sky_begin/end around the sky tiles' direct loop), by
 class: VALU arithmetic (v_add/mul/fma/...), VALU select/move (v_cndmask, v_mov),
 VALU compare, SALU, LDS, VMEM, branch/exec.  Diagnostic for where the kernel's
 non-arithmetic instructions sit.
@@ -60,7 +61,8 @@ def main():
         m = re.search(r";WOMARK (\w+)", line)
         if m:
             sec = {"cam_begin": "camera jobs", "collect_begin": "collect", "collect_end": "sweep",
-                   "shade_begin": "shade", "shade_end": "ring / accumulate", "take_begin": "take"}.get(m.group(1), m.group(1))
+                   "shade_begin": "shade", "shade_end": "ring / accumulate", "take_begin": "take",
+                   "sky_begin": "sky tiles", "sky_end": "after sky tiles"}.get(m.group(1), m.group(1))
             continue
         t = line.strip()
         if not t or t.startswith((";", ".", "_")) or t.endswith(":"):
