@@ -114,6 +114,9 @@ typedef struct Gen {
     int tile_cull;
     uint32_t nterm, term_bit0;
     struct TEnt *tgroups, *tterms;
+    /* the sky-ray predicate is being written (gen_sky_rays): a lane's own tests, so no
+     * wave-level member skip (a met interval only narrows: the same emptiness) */
+    int sky;
     int err;
 } Gen;
 
@@ -153,7 +156,7 @@ static void gen_members(Gen* g, uint32_t pc, uint32_t cnt, int indent) {
         const WoRec* L = &g->prog[pc + 1 + m];
         uint32_t vl[4];
         for (int i = 0; i < 4; ++i) vl[i] = fbits(L->f[i]);
-        if (m > 0) /* empty on every lane: the other members cannot widen it */
+        if (m > 0 && !g->sky) /* empty on every lane: the other members cannot widen it */
             bput(g->b, "%*s  if (__ballot(!(iv.a > iv.b)) != 0ull) {\n", indent, ""), ++open_skips;
         bput(g->b, "%*s  {\n", indent, "");
         const WoRec* L2 = m + 1u < cnt ? &g->prog[pc + 2 + m] : NULL;
@@ -419,6 +422,52 @@ static void gen_sprim(Gen* g, const SPrim* q, int indent) {
     for (uint32_t k = 0; k < q->npc; ++k) gen_collect(g, q->pcs[k], q->pcs[k] + 1u + g->prog[q->pcs[k]].u0, indent);
 }
 
+/* A group's bound test on its lane's ray, up to `miss` (c - o and tca + R with the
+ * constants as VALU literal operands; R^2, an FMA addend, in an SGPR): the collect's
+ * first pass and the sky-ray predicate (gen_sky_rays) both write it from here. */
+static void put_group_miss(Gen* g, const SPrim* p, uint32_t n, int indent) {
+    double c[3], R;
+    sprim_bound(p, n, c, &R);
+    const float fc[3] = {(float)c[0], (float)c[1], (float)c[2]};
+    const float fR = (float)R, fR2 = (float)(R * R);
+    uint32_t vr2 = fbits(fR2);
+    static const char* nr[1] = {"bc3"};
+    bput(g->b, "%*s  WO_WK(WO_WORK_BOUND_TESTS);\n", indent, "");
+    emit_consts(g->b, indent + 2, "float", nr, &vr2, 1);
+    bput(g->b,
+         "%*s  float ox, oy, oz, tca, d2, tr;\n"
+         "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(ox) : \"v\"(o.x));\n"
+         "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(oy) : \"v\"(o.y));\n"
+         "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(oz) : \"v\"(o.z));\n"
+         "%*s  wodev::bound_tca_d2(ox, oy, oz, d, tca, d2);\n"
+         "%*s  asm(\"v_add_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(tr) : \"v\"(tca));\n"
+         "%*s  const bool miss = (d2 > __builtin_fmaf(4e-6f * tca, tca, bc3)) | (tr < 0.0f);\n",
+         indent, "", indent, "", fbits(fc[0]), indent, "", fbits(fc[1]), indent, "", fbits(fc[2]), indent, "",
+         indent, "", fbits(fR), indent, "");
+}
+
+/* The surface-area split of p[0..n) (csg32 3.716 -> 3.586 ms against median splits):
+ * over the three axes (centres sorted) and every cut, the least R_left^2 * n_left +
+ * R_right^2 * n_right of the enclosing spheres.  Sorts p along the chosen axis and
+ * returns the cut. */
+static uint32_t spatial_cut(SPrim* p, uint32_t n) {
+    uint32_t cut = n / 2u;
+    int ax = 0;
+    double best = -1.0;
+    for (int a = 0; a < 3; ++a) {
+        qsort(p, n, sizeof(SPrim), a == 0 ? sprim_cmp0 : a == 1 ? sprim_cmp1 : sprim_cmp2);
+        for (uint32_t k = 1; k < n; ++k) {
+            double cl[3], cr[3], rl, rr;
+            sprim_bound(p, k, cl, &rl);
+            sprim_bound(p + k, n - k, cr, &rr);
+            const double cost = rl * rl * k + rr * rr * (n - k);
+            if (best < 0.0 || cost < best) best = cost, ax = a, cut = k;
+        }
+    }
+    qsort(p, n, sizeof(SPrim), ax == 0 ? sprim_cmp0 : ax == 1 ? sprim_cmp1 : sprim_cmp2);
+    return cut;
+}
+
 static void gen_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root) {
     if (n == 0u || g->err) return;
     if (n == 1u) {
@@ -427,38 +476,23 @@ static void gen_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root) {
     }
     int inner = indent;
     if (!root) {
-        double c[3], R;
-        sprim_bound(p, n, c, &R);
         const uint32_t k = g->nbound++;
         if (g->first_pass) {
-            const float fc[3] = {(float)c[0], (float)c[1], (float)c[2]};
-            const float fR = (float)R, fR2 = (float)(R * R);
-            uint32_t vr2 = fbits(fR2);
-            static const char* nr[1] = {"bc3"};
             uint32_t nprim = 0;
             for (uint32_t i = 0; i < n; ++i) nprim += p[i].npc ? p[i].npc : 1u;
             if (g->tgroups) {
+                double c[3], R;
+                sprim_bound(p, n, c, &R);
                 TEnt* e = &g->tgroups[k];
                 e->kind = 1;
-                for (int a = 0; a < 3; ++a) e->a[a] = fc[a], e->b[a] = 0.0f;
-                e->b[0] = fR;
+                for (int a = 0; a < 3; ++a) e->a[a] = (float)c[a], e->b[a] = 0.0f;
+                e->b[0] = (float)R;
             }
             /* with the tile pre-cull a bit may be set on entry: the test runs only when it is not */
             bput(g->b, "%*s{  // group %u (%u primitives)\n", indent, "", k, nprim);
             if (g->tile_cull) bput(g->b, "%*s  if ((cull[%u] & %uu) == 0u) {\n", indent, "", k / 32, 1u << (k % 32));
-            bput(g->b, "%*s  WO_WK(WO_WORK_BOUND_TESTS);\n", indent, "");
-            emit_consts(g->b, indent + 2, "float", nr, &vr2, 1);
-            bput(g->b,
-                 "%*s  float ox, oy, oz, tca, d2, tr;\n"
-                 "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(ox) : \"v\"(o.x));\n"
-                 "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(oy) : \"v\"(o.y));\n"
-                 "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(oz) : \"v\"(o.z));\n"
-                 "%*s  wodev::bound_tca_d2(ox, oy, oz, d, tca, d2);\n"
-                 "%*s  asm(\"v_add_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(tr) : \"v\"(tca));\n"
-                 "%*s  const bool miss = (d2 > __builtin_fmaf(4e-6f * tca, tca, bc3)) | (tr < 0.0f);\n"
-                 "%*s  if (__ballot(!miss) == 0ull) cull[%u] |= %uu;\n",
-                 indent, "", indent, "", fbits(fc[0]), indent, "", fbits(fc[1]), indent, "", fbits(fc[2]), indent, "",
-                 indent, "", fbits(fR), indent, "", indent, "", k / 32, 1u << (k % 32));
+            put_group_miss(g, p, n, indent);
+            bput(g->b, "%*s  if (__ballot(!miss) == 0ull) cull[%u] |= %uu;\n", indent, "", k / 32, 1u << (k % 32));
             if (g->tile_cull) bput(g->b, "%*s  }\n", indent, "");
             bput(g->b, "%*s}\n%*sif (!(cull[%u] & %uu)) {\n", indent, "", indent, "", k / 32, 1u << (k % 32));
         } else {
@@ -469,23 +503,7 @@ static void gen_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root) {
     if (n <= g->spatial_leaf) {
         for (uint32_t i = 0; i < n; ++i) gen_sprim(g, &p[i], inner);
     } else {
-        /* surface-area split (csg32 3.716 -> 3.586 ms against median splits): over
-         * the three axes (centres sorted) and every cut, the least R_left^2 * n_left
-         * + R_right^2 * n_right of the enclosing spheres */
-        uint32_t cut = n / 2u;
-        int ax = 0;
-        double best = -1.0;
-        for (int a = 0; a < 3; ++a) {
-            qsort(p, n, sizeof(SPrim), a == 0 ? sprim_cmp0 : a == 1 ? sprim_cmp1 : sprim_cmp2);
-            for (uint32_t k = 1; k < n; ++k) {
-                double cl[3], cr[3], rl, rr;
-                sprim_bound(p, k, cl, &rl);
-                sprim_bound(p + k, n - k, cr, &rr);
-                const double cost = rl * rl * k + rr * rr * (n - k);
-                if (best < 0.0 || cost < best) best = cost, ax = a, cut = k;
-            }
-        }
-        qsort(p, n, sizeof(SPrim), ax == 0 ? sprim_cmp0 : ax == 1 ? sprim_cmp1 : sprim_cmp2);
+        const uint32_t cut = spatial_cut(p, n);
         gen_spatial(g, p, cut, inner, 0);
         gen_spatial(g, p + cut, n - cut, inner, 0);
     }
@@ -739,6 +757,29 @@ static void term_tile_ent(const Gen* g, const SPrim* q, TEnt* e) {
     for (int a = 0; a < 3; ++a) e->a[a] = (float)lo[a], e->b[a] = (float)hi[a]; /* fp32 values: exact */
 }
 
+/* A lone-sphere term's b, ll and disc on its lane's ray: sphere_need(b, disc) is the
+ * lane's side of the wave-level test that guards its interval and candidates. */
+static void put_lone_disc(Gen* g, const WoRec* L, int indent) {
+    uint32_t vl[4];
+    for (int i = 0; i < 4; ++i) vl[i] = fbits(L->f[i]);
+    bput(g->b,
+         "%*s  WO_WK(WO_WORK_SPHERE_TESTS);\n"
+         "%*s  float fx, fy, fz, b, ll, disc;\n"
+         "%*s  asm(\"v_subrev_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(fx) : \"v\"(o.x));\n"
+         "%*s  asm(\"v_subrev_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(fy) : \"v\"(o.y));\n"
+         "%*s  asm(\"v_subrev_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(fz) : \"v\"(o.z));\n"
+         "%*s  wodev::sphere_fbl(fx, fy, fz, d, b, ll);\n"
+         "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(disc) : \"v\"(ll));\n",
+         indent, "", indent, "", indent, "", vl[0], indent, "", vl[1], indent, "", vl[2], indent, "", indent, "",
+         vl[3]);
+}
+
+/* Whether a term's positive first literal (interval `ia`) reaches past t_min on this
+ * lane: where it does not, the term is false along the whole ray and forms no
+ * candidate (term_lit's `valid`).  gen_term_body ballots it around a two-literal
+ * term's second literal and candidates; gen_sky_rays tests it per lane. */
+#define JIT_TERM_REACH "!(ia.a > ia.b) & (ia.b > tmin)"
+
 /* One term behind its bit of cull[] (set only by the tile pre-cull). */
 static void gen_term(Gen* g, const SPrim* q, int indent) {
     if (!g->tile_cull) {
@@ -773,16 +814,8 @@ static void gen_term_body(Gen* g, const SPrim* q, int indent) {
         /* a lone sphere: its interval is [-b - s, -b + s] exactly when disc >= 0, so
          * its transitions are formed inside the branch that computes s */
         const WoRec* L = &g->prog[pcs[0] + 1u];
-        uint32_t vl[4];
-        for (int i = 0; i < 4; ++i) vl[i] = fbits(L->f[i]);
+        put_lone_disc(g, L, indent);
         bput(g->b,
-             "%*s  WO_WK(WO_WORK_SPHERE_TESTS);\n"
-             "%*s  float fx, fy, fz, b, ll, disc;\n"
-             "%*s  asm(\"v_subrev_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(fx) : \"v\"(o.x));\n"
-             "%*s  asm(\"v_subrev_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(fy) : \"v\"(o.y));\n"
-             "%*s  asm(\"v_subrev_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(fz) : \"v\"(o.z));\n"
-             "%*s  wodev::sphere_fbl(fx, fy, fz, d, b, ll);\n"
-             "%*s  asm(\"v_sub_f32_e32 %%0, 0x%08x, %%1\" : \"=v\"(disc) : \"v\"(ll));\n"
              "%*s  if (__ballot(wodev::sphere_need(b, disc)) != 0ull) {\n"
              "%*s    asm volatile(\"\");\n"
              "#if WO_LONE_SEL  // every lane of the wave forms the interval; hd masks the candidates\n"
@@ -796,8 +829,7 @@ static void gen_term_body(Gen* g, const SPrim* q, int indent) {
              "%*s      uint32_t ka, kb;\n"
              "%*s      asm volatile(\"s_mov_b32 %%0, 0x%08x\\n\\ts_mov_b32 %%1, 0x%08x\" : \"=s\"(ka), \"=s\"(kb));\n"
              "%*s      const uint64_t k0 = wodev::event_key_lo(la, ka), k1 = wodev::event_key_lo(lb, kb);\n",
-             indent, "", indent, "", indent, "", vl[0], indent, "", vl[1], indent, "", vl[2], indent, "", indent, "",
-             vl[3], indent, "", indent, "", indent, "", indent, "", indent, "", indent, "", indent, "", indent, "",
+             indent, "", indent, "", indent, "", indent, "", indent, "", indent, "", indent, "", indent, "",
              indent, "", term_ka(o0, 1), term_kb(o0, 1), indent, "");
         if (first) bput(g->b, "%*s      cnt += (hd & (la <= tmin) & (lb > tmin)) ? 1u : 0u;\n", indent, "");
         bput(g->b,
@@ -827,7 +859,7 @@ static void gen_term_body(Gen* g, const SPrim* q, int indent) {
     vk[3] = term_kb(o1, pos[1]);
     /* a positive first literal empty along every lane's ray: the term is false throughout */
     if (pos[0])
-        bput(g->b, "%*s  if (__ballot(!(ia.a > ia.b) & (ia.b > tmin)) != 0ull) {\n", indent, "");
+        bput(g->b, "%*s  if (__ballot(" JIT_TERM_REACH ") != 0ull) {\n", indent, "");
     else
         bput(g->b, "%*s  {\n", indent, "");
     bput(g->b, "%*s    wodev::Ivl ib;\n", indent, "");
@@ -847,6 +879,126 @@ static void gen_term_body(Gen* g, const SPrim* q, int indent) {
          indent, "", indent, "", pos[1] ? "true" : "false", first ? "true" : "false", o1 < o0 ? "true" : "false",
          indent, "", pos[0] ? "true" : "false", first ? "true" : "false", o0 < o1 ? "true" : "false", indent, "",
          indent, "");
+}
+
+/* ---- sky rays ----
+ * bool ray_misses_scene(o, d) const, beside trace: true on a lane only when each bound
+ * of the chosen level reports `miss` for the lane's ray and each term that level
+ * leaves ungrouped does not reach past t_min on it.  The tests are written by the
+ * collect's own emitters (put_group_miss, gen_term_ivl and JIT_TERM_REACH,
+ * put_lone_disc), so they are the first pass's arithmetic on its constants: a wave
+ * whose lanes all satisfied it would cull each of those groups by its ballot, enter no
+ * such term, and leave the collect with no candidate -- and a lane's trace result does
+ * not depend on the other lanes' rays.  pathtrace_block ends such a path on the sky
+ * where it scatters (wo_device_common.h TracerSkyRays).
+ * Level 1 tests the hierarchy's top groups; level 2 replaces a top group that has
+ * child groups by those (a lone term under it by its own test).  (Every group opened
+ * down to the terms accepts 69 % of csg32's scattered rays against 38 %, but its 13
+ * term tests spill 72 B a lane to scratch: 2.79 ms against 2.37)  A term without such a
+ * test (its first literal complemented) keeps the group above it, and the predicate is
+ * left out where that is the root. */
+
+#define JIT_SKY_LEVELS 2
+/* a term's test: `gone = gone & <the term cannot be met>`; 0 when it has none */
+static int gen_sky_term(Gen* g, const SPrim* q, int indent) {
+    if (!q->term || !q->npc) return 0;
+    uint32_t pc0 = q->pcs[0];
+    int pos0 = !(q->negm & 1u);
+    if (q->npc > 1u && !pos0 && !(q->negm & 2u)) pc0 = q->pcs[1], pos0 = 1; /* gen_term_body's order */
+    if (!pos0) return 0;
+    const WoRec* P = &g->prog[pc0];
+    bput(g->b, "%*s{  // a term on its own: primitive %u\n", indent, "", P->u1);
+    if (q->npc == 1u && P->u0 == 1u && g->prog[pc0 + 1u].op == WO_LEAF_SPHERE) {
+        put_lone_disc(g, &g->prog[pc0 + 1u], indent);
+        bput(g->b, "%*s  gone = gone & !wodev::sphere_need(b, disc);\n%*s}\n", indent, "", indent, "");
+        return 1;
+    }
+    bput(g->b, "%*s  wodev::Ivl ia;\n", indent, "");
+    gen_term_ivl(g, pc0, "ia", indent + 2);
+    bput(g->b, "%*s  gone = gone & !(" JIT_TERM_REACH ");\n%*s}\n", indent, "", indent, "");
+    return 1;
+}
+
+/* p[0..n) as gen_spatial groups it; `level` counts the groups still to be opened */
+static int gen_sky_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root, int level) {
+    if (n == 0u) return 1;
+    if (n == 1u) return gen_sky_term(g, &p[0], indent);
+    if (root || (level > 1 && n > g->spatial_leaf)) {
+        /* the children instead, into a buffer of their own: kept only when each has a test */
+        Buf sub = {0};
+        Buf* keep = g->b;
+        g->b = &sub;
+        int ok = 1;
+        if (n <= g->spatial_leaf) {
+            for (uint32_t i = 0; i < n && ok; ++i) ok = gen_sky_term(g, &p[i], indent);
+        } else {
+            const uint32_t cut = spatial_cut(p, n);
+            const int below = root ? level : level - 1;
+            ok = gen_sky_spatial(g, p, cut, indent, 0, below) && gen_sky_spatial(g, p + cut, n - cut, indent, 0, below);
+        }
+        g->b = keep;
+        if (sub.oom) g->err = 1;
+        if (ok && sub.s) bput(g->b, "%s", sub.s);
+        free(sub.s);
+        if (ok || root) return ok;
+    }
+    uint32_t nprim = 0;
+    for (uint32_t i = 0; i < n; ++i) nprim += p[i].npc ? p[i].npc : 1u;
+    bput(g->b, "%*s{  // a group's bound (%u primitives)\n", indent, "", nprim);
+    put_group_miss(g, p, n, indent);
+    bput(g->b, "%*s  gone = gone & miss;\n%*s}\n", indent, "", indent, "");
+    return 1;
+}
+
+/* The predicate of `level` into g->b (term mode); 0, and nothing written, when the
+ * scene has no such predicate. */
+static int gen_sky_rays(Gen* g, int level) {
+    if (!g->term_mode || !g->nsprims) return 0;
+    SPrim* p = (SPrim*)malloc(sizeof(SPrim) * g->nsprims);
+    if (!p) {
+        g->err = 1;
+        return 0;
+    }
+    memcpy(p, g->sprims, sizeof(SPrim) * g->nsprims); /* gen_spatial's order */
+    Buf body = {0};
+    Buf* keep = g->b;
+    g->b = &body;
+    g->sky = 1;
+    int ok = 1;
+    for (uint32_t i = 0; i < g->ntunb && ok; ++i) ok = gen_sky_term(g, &g->tunb[i], 4);
+    ok = ok && gen_sky_spatial(g, p, g->nsprims, 4, 1, level);
+    g->sky = 0;
+    g->b = keep;
+    free(p);
+    if (body.oom) g->err = 1;
+    if (ok && body.s && !g->err) {
+        /* (the header's functions by a using-directive, not by their qualified names:
+         * tests/test_jit.py counts the collect passes' leaf tests by those, one per leaf
+         * and pass, and this is not a pass) */
+        bput(g->b,
+             "  __device__ __forceinline__ bool ray_misses_scene(wodev::F3 o, wodev::F3 d) const {\n"
+             "    using namespace wodev;\n"
+             "    const float tmin = WO_T_MIN;\n");
+        for (int a = 0; a < 3; ++a) { /* the reciprocals its axis faces use */
+            const char name[4] = {'i', 'v', "xyz"[a], 0};
+            if (strstr(body.s, name)) bput(g->b, "    const float iv%c = rcp_dir(d.%c);\n", "xyz"[a], "xyz"[a]);
+        }
+        bput(g->b, "    (void)tmin;\n    bool gone = true;\n");
+        for (const char* s = body.s; *s;) {
+            const char* q = strstr(s, "wodev::");
+            if (!q) {
+                bput(g->b, "%s", s);
+                break;
+            }
+            bput(g->b, "%.*s", (int)(q - s), s);
+            s = q + 7;
+        }
+        bput(g->b, "    return gone;\n  }\n");
+    } else {
+        ok = 0;
+    }
+    free(body.s);
+    return ok;
 }
 
 /* ---- eval, flattened: literal sets as one masked compare ----
@@ -2483,6 +2635,21 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
         }
         bput(&b, "};\n");
     }
+    /* the sky-ray predicates by level (gen_sky_rays), written after trace */
+    Buf sky[JIT_SKY_LEVELS];
+    memset(sky, 0, sizeof sky);
+    int have_sky = 0;
+    for (int L = 0; L < JIT_SKY_LEVELS && g.term_mode && !g.err; ++L) {
+        g.b = &sky[L];
+        const int ok = gen_sky_rays(&g, L + 1);
+        g.b = &b;
+        if (sky[L].oom) g.err = 1;
+        if (L == 0) have_sky = ok;
+        if (!ok) break;
+    }
+    /* level 2 by default (csg32, 1920x1080x64: 2.428 ms without the predicate, 2.413 at
+     * level 1, 2.369 at level 2; profiles/sky_rays_ab.txt) */
+    if (have_sky) bput(&b, "#ifndef WO_SKY_RAYS\n#define WO_SKY_RAYS 2  // 0: no sky-ray predicate; 1, 2: its level\n#endif\n");
     bput(&b, "struct JitTracer {\n");
     if (n_tile) {
         bput(&b,
@@ -2498,7 +2665,7 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
     }
     bput(&b,
          "  static constexpr bool kCount = WO_COUNT_WORK != 0;  // counting variant: -DWO_COUNT_WORK=1\n"
-         "  wodev::WorkCounts wk;\n"
+         "  %swodev::WorkCounts wk;\n"
          "  uint64_t tmark;  // end of the first pass (section timing)\n"
          "  const WoRec* __restrict__ prog;\n"
          "  const uint32_t* __restrict__ ordpc;\n"
@@ -2519,7 +2686,8 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
          "  __device__ __forceinline__ WoRec hit_leaf(const wodev::Hit& h) const {\n"
          "    return prog[ordpc[h.ord()] + 1u + h.member()];\n"
          "  }\n"
-         "  __device__ __forceinline__ bool trace(wodev::F3 o, wodev::F3 d, wodev::Hit& hit) {\n");
+         "  __device__ __forceinline__ bool trace(wodev::F3 o, wodev::F3 d, wodev::Hit& hit) {\n",
+         have_sky ? "mutable " : ""); /* ray_misses_scene is const and counts its tests */
     if (n_prims == 0) {
         bput(&b, "    return false;\n  }\n};\n");
     } else {
@@ -2575,8 +2743,14 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
                  "      }\n"
                  "      if (best == wodev::kBestNone) return false;\n"
                  "    }\n"
-                 "  }\n"
-                 "};\n");
+                 "  }\n");
+            if (have_sky) {
+                bput(&b, "  // WO_SKY_RAYS_BEGIN (host-compiled by tests/test_sky_rays.py)\n");
+                for (int L = 0; L < JIT_SKY_LEVELS && sky[L].s; ++L)
+                    bput(&b, "#%s WO_SKY_RAYS == %d\n%s", L ? "elif" : "if", L + 1, sky[L].s);
+                bput(&b, "#endif\n  // WO_SKY_RAYS_END\n");
+            }
+            bput(&b, "};\n");
             eval_ops = 4;
             goto kernel_tail;
         }
@@ -2936,6 +3110,7 @@ kernel_tail:
      * 3 for every tree since bench.py's renders stopped sharing a hardware queue (the
      * chain kept 8 before: 6.88 -> 6.99x at N = 8 with 3 now) */
     bput(&b, "// wo_share_tiles %u\n", 3u);
+    for (int L = 0; L < JIT_SKY_LEVELS; ++L) free(sky[L].s);
     free(g.dls);
     free(lut.table);
     hplan_free(&hl);

@@ -62,7 +62,8 @@ def main():
         if m:
             sec = {"cam_begin": "camera jobs", "collect_begin": "collect", "collect_end": "sweep",
                    "shade_begin": "shade", "shade_end": "ring / accumulate", "take_begin": "take",
-                   "sky_begin": "sky tiles", "sky_end": "after sky tiles"}.get(m.group(1), m.group(1))
+                   "sky_begin": "sky tiles", "sky_end": "after sky tiles",
+                   "sky_ray_begin": "sky rays", "sky_ray_end": "shade"}.get(m.group(1), m.group(1))
             continue
         t = line.strip()
         if not t or t.startswith((";", ".", "_")) or t.endswith(":"):

@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""The share of csg32's scattered rays that the sky-ray predicate (WO_SKY_RAYS, scene_jit.c
+gen_sky_rays) accepts, by level, and what ending them at the scatter does to the frame time.
+
+Share, on the GPU: the probe build (-DWO_SKY_RAYS_PROBE=1) runs the predicate where the
+default build does but ends no path; it adds one to the segment counter per accepted ray.
+With S the plain frame's segments and P its primary segments (pixels x spp), S - P rays
+were scattered and went on, and
+
+    p(level) = (segments of the level's probe build - S) / (S - P).
+
+--cpu gives the same share from the CPU oracle over Lambertian scatters of the scene's
+camera rays (the predicate compiled on the host, tests/test_sky_rays.py), with the share of
+those rays that hit nothing.
+
+--ab N times wo_renderer_render_rows_device (HIP events, prewarm, --frames frames a run) of
+the listed levels in N alternating rounds.  Needs a GPU except with --cpu alone; not a
+test, not bench.py.
+
+    python tools/sky_ray_share.py --out profiles/sky_rays_before.txt
+    python tools/sky_ray_share.py --ab 4 --levels 0,1,2
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def cpu_share(say, n_cam):
+    """The predicate on the host against the oracle (the test's harness)."""
+    import pathlib
+    import tempfile
+
+    import numpy as np
+    import test_sky_rays as t
+
+    built = t.build_harness(pathlib.Path(tempfile.mkdtemp(prefix="sky_rays")))
+    for scene in t.SCENES:
+        s = built[scene]
+        o, d = t._scattered(s, np.random.default_rng(1), n_cam)
+        for level in t.LEVELS:
+            pred, hit, _ = t._check(s, level, o, d)
+            say(f"cpu {scene} level {level}: {len(o)} scattered rays, {100.0 * (~hit).mean():.1f} % hit nothing, "
+                f"predicate accepts {100.0 * pred.mean():.1f} %, accepted rays with a hit: {int((pred & hit).sum())}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", default="csg32")
+    ap.add_argument("--levels", default="1,2")
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--prewarm-s", type=float, default=0.3)
+    ap.add_argument("--ab", type=int, default=0, help="alternating rounds timing the levels (0 included as listed)")
+    ap.add_argument("--cpu", action="store_true", help="the oracle's share too")
+    ap.add_argument("--cpu-rays", type=int, default=20000, help="--cpu: camera rays")
+    ap.add_argument("--no-gpu", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    levels = [int(x) for x in a.levels.split(",")]
+    if not a.no_gpu:
+        import torch  # (before libwololo.so: one HIP runtime in the process)
+        from csgrenderer_amd import scenes
+        from csgrenderer_amd import wololo as wl
+
+        def renderer(flags):
+            os.environ["WOLOLO_JIT_FLAGS"] = flags
+            r = wl.Renderer(a.scene, max_nodes=4096)
+            info = scenes.build(a.scene, r)
+            r.set_tracer("jit")
+            r.prepare()
+            return r, info.params()
+
+        out = torch.zeros((1080, 1920, 4), dtype=torch.float32, device="cuda")
+        seg = torch.zeros(1, dtype=torch.int64, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+
+        def segments(r, p):
+            seg.zero_()
+            r.render_rows_device(p, out.data_ptr(), 4, 0, 1, stream, seg.data_ptr())
+            torch.cuda.synchronize()
+            return int(seg.item())
+
+        def frame_ms(r, p):
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < a.prewarm_s:
+                r.render_rows_device(p, out.data_ptr(), 4, 0, 1, stream, 0)
+                torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.frames)]
+            for x, y in ev:
+                x.record()
+                r.render_rows_device(p, out.data_ptr(), 4, 0, 1, stream, 0)
+                y.record()
+            torch.cuda.synchronize()
+            return statistics.median(x.elapsed_time(y) for x, y in ev)
+
+        if a.ab:
+            rs = [(L,) + renderer(f"-DWO_SKY_RAYS={L}") for L in levels]
+            say(f"{a.scene} {rs[0][2].width}x{rs[0][2].height} {rs[0][2].spp} spp depth {rs[0][2].max_depth}: median of "
+                f"{a.frames} frames a run, {a.ab} alternating rounds")
+            ms = {L: [] for L in levels}
+            for i in range(a.ab):
+                for L, r, p in rs:
+                    ms[L].append(frame_ms(r, p))
+                say(f"round {i + 1}: " + ", ".join(f"level {L} {ms[L][-1]:.4f} ms" for L in levels))
+            for L, r, p in rs:
+                k = r.kernel_info()
+                say(f"level {L}: median {statistics.median(ms[L]):.4f} ms, spread {max(ms[L]) - min(ms[L]):.4f}; kernel "
+                    f"{k['key'][:16]}, {k['vgprs']} VGPRs, {k['scratch_bytes']} B scratch, {k['lds_bytes']} B LDS, "
+                    f"{segments(r, p)} segments")
+                r.close()
+        else:
+            r, p = renderer("-DWO_SKY_RAYS=0")
+            S, P = segments(r, p), p.width * p.height * p.spp
+            r.close()
+            say(f"{a.scene} {p.width}x{p.height} {p.spp} spp depth {p.max_depth}: {S} segments, {P} primary, "
+                f"{S - P} scattered rays that go on ({S / P:.4f} segments per path)")
+            for L in levels:
+                if L == 0:
+                    continue
+                r, p = renderer(f"-DWO_SKY_RAYS={L} -DWO_SKY_RAYS_PROBE=1")
+                n = segments(r, p) - S
+                say(f"gpu level {L}: the predicate accepts {n} of them, p = {100.0 * n / (S - P):.2f} %")
+                r.close()
+                r, p = renderer(f"-DWO_SKY_RAYS={L}")
+                s2 = segments(r, p)
+                say(f"gpu level {L}: the build that ends them counts {s2} segments ({'the same' if s2 == S else 'DIFFERENT'})")
+                r.close()
+    if a.cpu:
+        os.environ.setdefault("WOLOLO_ALLOW_NO_DEVICE", "1")
+        cpu_share(say, a.cpu_rays)
+    if a.out:
+        open(a.out, "w").write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
