@@ -10,17 +10,11 @@
 //                      postfix program (staged in LDS when it fits), wave-uniform
 //                      BOUND culling, sorted event window, bit-stack evaluation.
 //   wo_jit_pathtrace   the same path tracer SPECIALISED per scene: source from
-//                      scene_jit.c, compiled here with hiprtc at scene upload.
+//                      scene_jit.c, compiled and cached by jit_code.cpp, loaded here.
 //   assemble_kernel    un-interleaves row-cyclic rank tiles after the gather.
 // The shared device code (math, RNG, leaves, event window, shading, path loop)
 // is wo_device_common.h; both forms agree bit-for-bit with oracle/oracle.c.
 #include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
-#include <dlfcn.h>
-#include <limits.h>
-#include <spawn.h>
-#include <sys/wait.h>
-#include <unistd.h>
 
 #include <stdint.h>
 #include <stdio.h>
@@ -28,16 +22,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <array>
-#include <atomic>
-#include <chrono>
 #include <cmath>
 #include <mutex>
 #include <string>
-#include <thread>
-#include <unordered_map>
 #include <vector>
 
+#include "jit_code.h"
 #include "wo_dev.h"
 // the static kernels raise the wave priority while a hit's leaf and material loads issue
 // (RTIOW cover 11.50 -> 11.47 ms in two pairs; the specialised kernel keeps 0: csg32 3.261 vs 3.266)
@@ -47,7 +37,6 @@
 #include "wo_device_common.h"
 #include "wololo/wo_scene.h"
 
-#include "jit_sources.inc"
 #include "static_key.inc"  // WO_STATIC_SRC_SHA: the library kernels' source identity
 
 #pragma clang fp contract(off)
@@ -1613,7 +1602,7 @@ struct WoDev {
     int peer_mode;  // how this rank's share reaches the root (WO_PEER_*; wo_dev_enable_peer)
     unsigned long long* d_segacc;  // segments of this rank's device frames (wo_dev_take_segments)
     bool lanes_on;
-    // scene-specialised kernel (hiprtc)
+    // scene-specialised kernel (its code object: jit_code.cpp)
     hipModule_t jit_module;
     hipFunction_t jit_fn;
     uint32_t jit_share_tiles;  // big tiles per resident workgroup for the specialised kernel (plan_tiles)
@@ -1835,319 +1824,7 @@ extern "C" int wo_dev_upload_scene(WoDev* dev, WoRec const* prog, uint32_t n_rec
                                     err, errlen);
 }
 
-// ---- scene-specialised kernels (hiprtc) ----
-
-// Process-wide cache of compiled code objects (the same scene compiled once per
-// process, loaded on every rank), in front of the on-disk cache (jit_cache.c)
-// shared by processes.  Bounded: the least recently used entries go beyond
-// kJitCacheEntries (an interactive session that edits the scene would otherwise
-// keep every version's object, megabytes each; the disk cache still has them).
-struct JitEntry {
-    std::vector<char> code;
-    uint64_t used;
-};
-static const size_t kJitCacheEntries = 8;
-// The process cache and its lock live on the heap and are never destroyed: a
-// background compile still running when the process exits (a renderer never
-// closed) then touches no destroyed static.
-static std::mutex& g_jit_mu = *new std::mutex;
-static uint64_t g_jit_tick;
-static std::unordered_map<std::string, JitEntry>& jit_cache() {
-    static auto* m = new std::unordered_map<std::string, JitEntry>;
-    return *m;
-}
-static void jit_cache_put(const std::string& key, const std::vector<char>& code) {  // g_jit_mu held
-    auto& m = jit_cache();
-    m[key] = JitEntry{code, ++g_jit_tick};
-    while (m.size() > kJitCacheEntries) {
-        auto old = m.begin();
-        for (auto it = m.begin(); it != m.end(); ++it)
-            if (it->second.used < old->second.used) old = it;
-        m.erase(old);
-    }
-}
-
-// Extra hiprtc options from WOLOLO_JIT_FLAGS (space separated), e.g.
-// "-DWO_WINDOW=2 -DWO_JIT_MIN_WAVES=4" -- a tuning knob; part of the cache key.
-static std::vector<std::string> jit_extra_flags() {
-    std::vector<std::string> out;
-    const char* e = getenv("WOLOLO_JIT_FLAGS");
-    if (!e) return out;
-    std::string s(e), cur;
-    for (char c : s) {
-        if (c == ' ') {
-            if (!cur.empty()) out.push_back(cur);
-            cur.clear();
-        } else {
-            cur.push_back(c);
-        }
-    }
-    if (!cur.empty()) out.push_back(cur);
-    return out;
-}
-
-// `count`: the counting variant (executed-work counters, wo_dev_count_work)
-static std::vector<std::string> jit_options(const std::string& arch, bool count) {
-    // no SLP vectorisation: its packed fp32 pairs need register moves to form and
-    // shorten no dependent chain (csg32 4.14 -> 4.05 ms, csg256 balanced 12.50 -> 12.08);
-    // WOLOLO_JIT_FLAGS=-fslp-vectorize turns it back on
-    std::vector<std::string> opts = {"--offload-arch=" + arch, "-O3", "-ffp-contract=off", "-std=c++17",
-                                     "-fno-slp-vectorize"};
-    for (const std::string& f : jit_extra_flags()) opts.push_back(f);
-    if (count) opts.push_back("-DWO_COUNT_WORK=1");
-    return opts;
-}
-
-// The compiler process (wo_jitc, next to this library): used when the hiprtc that
-// serves this process is not the system ROCm's -- a process that imported torch first
-// runs the library on torch's bundled HIP runtime, hiprtc and comgr (the sonames are
-// shared), and that older compiler spilled csg32_nested's kernel (12 B per lane, 3 %
-// slower).  wo_jitc links only the system hiprtc, in a
-// process of its own.  "" = compile in this process (the system hiprtc serves it, the
-// helper is missing, or WOLOLO_JITC=0).
-extern "C" char** environ;
-static const std::string& jitc_path() {
-    static const std::string path = []() -> std::string {
-        const char* env = getenv("WOLOLO_JITC");
-        if (env && *env == '0') return std::string();
-        Dl_info di;
-        char rp[PATH_MAX], rr[PATH_MAX];
-        const char* root = getenv("ROCM_PATH");
-        if (dladdr((void*)&hiprtcCompileProgram, &di) && di.dli_fname && realpath(di.dli_fname, rp) &&
-            realpath(root && *root ? root : "/opt/rocm", rr) && strncmp(rp, rr, strlen(rr)) == 0)
-            return std::string();  // the system hiprtc already
-        if (!dladdr((void*)&jitc_path, &di) || !di.dli_fname) return std::string();
-        std::string lib(di.dli_fname);
-        const size_t slash = lib.rfind('/');
-        std::string p = (slash == std::string::npos ? std::string(".") : lib.substr(0, slash)) + "/wo_jitc";
-        return access(p.c_str(), X_OK) == 0 ? p : std::string();
-    }();
-    return path;
-}
-
-// One compile through wo_jitc: the source and the code object through a private
-// temporary directory.  False: no object (the caller compiles in this process).
-static bool jitc_compile(const char* src, const std::vector<std::string>& opts, std::vector<char>& code) {
-    const char* td = getenv("TMPDIR");
-    std::string dir = std::string(td && *td ? td : "/tmp") + "/wojitc.XXXXXX";
-    if (!mkdtemp(&dir[0])) return false;
-    const std::string in = dir + "/k.hip", out = dir + "/k.co";
-    bool ok = false;
-    if (FILE* f = fopen(in.c_str(), "wb")) {
-        const size_t n = strlen(src);
-        ok = fwrite(src, 1, n, f) == n;
-        ok = (fclose(f) == 0) && ok;
-    }
-    if (ok) {
-        std::vector<char*> argv;
-        argv.push_back(const_cast<char*>(jitc_path().c_str()));
-        argv.push_back(const_cast<char*>(in.c_str()));
-        argv.push_back(const_cast<char*>(out.c_str()));
-        for (const std::string& o : opts) argv.push_back(const_cast<char*>(o.c_str()));
-        argv.push_back(nullptr);
-        pid_t pid;
-        int st = 0;
-        ok = posix_spawn(&pid, jitc_path().c_str(), nullptr, nullptr, argv.data(), environ) == 0 &&
-             waitpid(pid, &st, 0) == pid && WIFEXITED(st) && WEXITSTATUS(st) == 0;
-    }
-    if (ok) {
-        ok = false;
-        if (FILE* f = fopen(out.c_str(), "rb")) {
-            std::vector<char> buf;
-            char tmp[65536];
-            size_t n;
-            while ((n = fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + n);
-            fclose(f);
-            ok = buf.size() >= 4 && memcmp(buf.data(), "\x7f" "ELF", 4) == 0;
-            if (ok) code.swap(buf);
-        }
-    }
-    (void)unlink(in.c_str());
-    (void)unlink(out.c_str());
-    (void)rmdir(dir.c_str());
-    return ok;
-}
-
-static int jit_compile(const char* src, const std::string& arch, bool count, std::vector<char>& code, char* err,
-                       size_t errlen) {
-    if (!jitc_path().empty() && jitc_compile(src, jit_options(arch, count), code)) return 0;
-    hiprtcProgram p;
-    const char* hdr_src[] = {kEmbed_wo_device_common_h, kEmbed_wo_scene_h};
-    const char* hdr_names[] = {"wo_device_common.h", "wololo/wo_scene.h"};
-    if (hiprtcCreateProgram(&p, src, "wo_scene_jit.hip", 2, hdr_src, hdr_names) != HIPRTC_SUCCESS) {
-        snprintf(err, errlen, "hiprtcCreateProgram failed");
-        return -1;
-    }
-    std::vector<std::string> opt_s = jit_options(arch, count);
-    std::vector<const char*> opts;
-    for (const std::string& o : opt_s) opts.push_back(o.c_str());
-    hiprtcResult rc = hiprtcCompileProgram(p, (int)opts.size(), opts.data());
-    if (rc != HIPRTC_SUCCESS) {
-        size_t ls = 0;
-        hiprtcGetProgramLogSize(p, &ls);
-        std::string log(ls + 1, '\0');
-        hiprtcGetProgramLog(p, &log[0]);
-        snprintf(err, errlen, "hiprtc: %s: %.400s", hiprtcGetErrorString(rc), log.c_str());
-        hiprtcDestroyProgram(&p);
-        return -1;
-    }
-    size_t cs = 0;
-    hiprtcGetCodeSize(p, &cs);
-    code.resize(cs);
-    hiprtcGetCode(p, code.data());
-    hiprtcDestroyProgram(&p);
-    return 0;
-}
-
-// SHA-256 over everything the code object depends on: a format tag, the hiprtc
-// and HIP runtime versions, the target, the options (WOLOLO_JIT_FLAGS included), the embedded
-// headers and the generated source; each part length-prefixed.
-static std::string jit_key(const char* src, const std::string& arch, bool count = false) {
-    WoSha256 s;
-    wo_sha256_init(&s);
-    auto part = [&](const char* p, size_t n) {
-        const uint64_t len = n;
-        wo_sha256_update(&s, &len, sizeof len);
-        wo_sha256_update(&s, p, n);
-    };
-    part("wololo-jit-2", 12);
-    // the toolchain: hiprtc's major.minor and the HIP runtime's full version
-    // (patch level included: a ROCm update that changes the compiler or the
-    // device libraries misses instead of loading a stale object)
-    // (queried once: hiprtcVersion waits while another thread's compile holds
-    // hiprtc's lock, which stalled draw_frame behind a background compile)
-    static const std::array<int, 3> ver = []() {
-        int vmaj = 0, vmin = 0, vrt = 0;
-        (void)hiprtcVersion(&vmaj, &vmin);
-        (void)hipRuntimeGetVersion(&vrt);
-        return std::array<int, 3>{vmaj, vmin, vrt};
-    }();
-    part((const char*)ver.data(), sizeof(int) * ver.size());
-    // compiled by wo_jitc (the system hiprtc) rather than the hiprtc serving this process
-    if (!jitc_path().empty()) part("wo_jitc", 7);
-    part(arch.data(), arch.size());
-    for (const std::string& o : jit_options(arch, count)) part(o.data(), o.size());
-    part(kEmbed_wo_device_common_h, strlen(kEmbed_wo_device_common_h));
-    part(kEmbed_wo_scene_h, strlen(kEmbed_wo_scene_h));
-    part(src, strlen(src));
-    uint8_t dg[32];
-    wo_sha256_final(&s, dg);
-    char hex[65];
-    wo_sha256_hex(dg, hex);
-    return std::string(hex);
-}
-
-static int jit_code(const char* src, const std::string& arch, bool count, std::vector<char>& code, std::string& key,
-                    int& origin, double& seconds, char* err, size_t errlen) {
-    auto t0 = std::chrono::steady_clock::now();
-    key = jit_key(src, arch, count);
-    {
-        std::lock_guard<std::mutex> lock(g_jit_mu);
-        auto it = jit_cache().find(key);
-        if (it != jit_cache().end()) {
-            it->second.used = ++g_jit_tick;
-            code = it->second.code;
-            origin = 0;
-        }
-    }
-    if (code.empty()) {
-        void* buf = nullptr;
-        size_t n = 0;
-        if (wo_jit_disk_load(key.c_str(), &buf, &n) == 0) {
-            code.assign((char*)buf, (char*)buf + n);
-            free(buf);
-            origin = 1;
-        } else {
-            if (jit_compile(src, arch, count, code, err, errlen)) return -1;
-            origin = 2;
-            (void)wo_jit_disk_store(key.c_str(), code.data(), code.size());  // best effort
-        }
-        std::lock_guard<std::mutex> lock(g_jit_mu);
-        jit_cache_put(key, code);
-    }
-    seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return 0;
-}
-
-extern "C" long long wo_jit_code_object(const char* src, const char* arch, int* origin, double* seconds,
-                                        char* key_hex, char* err, size_t errlen) {
-    std::vector<char> code;
-    std::string key;
-    int org = -1;
-    double sec = 0.0;
-    if (jit_code(src, arch ? std::string(arch) : std::string("gfx950"), false, code, key, org, sec, err, errlen))
-        return -1;
-    if (origin) *origin = org;
-    if (seconds) *seconds = sec;
-    if (key_hex) snprintf(key_hex, 65, "%s", key.c_str());
-    return (long long)code.size();
-}
-
-// The group (LDS) and private (scratch per lane) segment sizes of kernel `name` as its
-// code object states them: the first two words of its AMDHSA kernel descriptor, the
-// symbol `<name>.kd` of the ELF's symbol table.  (hipFuncGetAttribute can answer for
-// another loaded module's kernel of the same name -- a second renderer's counting
-// variant -- so kernel_info reads the code object itself.)  False if `code` is not
-// such an ELF.
-static bool kd_segment_sizes(const std::vector<char>& code, const char* name, uint32_t* group, uint32_t* priv) {
-    const unsigned char* b = reinterpret_cast<const unsigned char*>(code.data());
-    const size_t n = code.size();
-    auto rd = [&](size_t off, size_t len, uint64_t* v) {
-        if (off > n || len > n - off) return false;
-        uint64_t x = 0;
-        for (size_t i = 0; i < len; ++i) x |= (uint64_t)b[off + i] << (8u * i);
-        *v = x;
-        return true;
-    };
-    if (n < 64 || memcmp(b, "\x7f" "ELF", 4) != 0 || b[4] != 2 || b[5] != 1) return false;  // ELF64, little-endian
-    uint64_t shoff, shentsize, shnum;
-    if (!rd(0x28, 8, &shoff) || !rd(0x3a, 2, &shentsize) || !rd(0x3c, 2, &shnum) || shentsize < 64) return false;
-    auto sh = [&](uint64_t i, size_t field, size_t len, uint64_t* v) { return rd(shoff + i * shentsize + field, len, v); };
-    const std::string want = std::string(name) + ".kd";
-    for (uint64_t i = 0; i < shnum; ++i) {
-        uint64_t type, off, size, link, entsize;
-        if (!sh(i, 4, 4, &type) || type != 2u) continue;  // SHT_SYMTAB
-        if (!sh(i, 24, 8, &off) || !sh(i, 32, 8, &size) || !sh(i, 40, 4, &link) || !sh(i, 56, 8, &entsize) ||
-            entsize < 24)
-            return false;
-        uint64_t stroff, strsize;
-        if (!sh(link, 24, 8, &stroff) || !sh(link, 32, 8, &strsize)) return false;
-        for (uint64_t k = 0; k + entsize <= size; k += entsize) {
-            uint64_t nm, shndx, value;
-            if (!rd(off + k, 4, &nm) || !rd(off + k + 6, 2, &shndx) || !rd(off + k + 8, 8, &value)) return false;
-            if (nm >= strsize || stroff + nm + want.size() + 1 > n) continue;
-            if (memcmp(b + stroff + nm, want.c_str(), want.size() + 1) != 0) continue;
-            uint64_t saddr, soff, g, p;
-            if (!sh(shndx, 16, 8, &saddr) || !sh(shndx, 24, 8, &soff) || value < saddr) return false;
-            if (!rd(soff + (value - saddr), 4, &g) || !rd(soff + (value - saddr) + 4, 4, &p)) return false;
-            *group = (uint32_t)g;
-            *priv = (uint32_t)p;
-            return true;
-        }
-    }
-    return false;
-}
-
-extern "C" int wo_jit_code_resources(const char* src, const char* arch, uint32_t* out, char* err, size_t errlen) {
-    std::vector<char> code;
-    std::string key;
-    int org = -1;
-    double sec = 0.0;
-    if (!src || !out) {
-        snprintf(err, errlen, "no source");
-        return -1;
-    }
-    if (jit_code(src, arch ? std::string(arch) : std::string("gfx950"), false, code, key, org, sec, err, errlen))
-        return -1;
-    uint32_t group = 0, priv = 0;
-    if (!kd_segment_sizes(code, "wo_jit_pathtrace", &group, &priv)) {
-        snprintf(err, errlen, "no kernel descriptor for wo_jit_pathtrace in the code object (%zu bytes)", code.size());
-        return -1;
-    }
-    out[0] = priv;
-    out[1] = group;
-    return 0;
-}
+// ---- scene-specialised kernels: their code objects are jit_code.cpp's; loaded here ----
 
 static int load_jit_module(const std::vector<char>& code, hipModule_t* mod, hipFunction_t* fn, char* err,
                            size_t errlen) {
@@ -2184,19 +1861,16 @@ extern "C" int wo_dev_set_jit(WoDev* dev, const char* src, char* err, size_t err
         dev->jit_origin = -1;
         return 0;
     }
-    std::vector<char> code;
-    std::string key;
-    int origin = -1;
-    double sec = 0.0;
-    if (dev->jit_fn && dev->jit_key == jit_key(src, dev->arch)) return 0;
-    if (jit_code(src, dev->arch, false, code, key, origin, sec, err, errlen)) return -1;
+    wojit::JitCode jc;
+    if (dev->jit_fn && dev->jit_key == wojit::jit_key(src, dev->arch)) return 0;
+    if (wojit::jit_code(src, dev->arch, false, &jc, err, errlen)) return -1;
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
-    if (load_jit_module(code, &mod, &fn, err, errlen)) return -1;
+    if (load_jit_module(jc.code, &mod, &fn, err, errlen)) return -1;
     if (dev->jit_module) (void)hipModuleUnload(dev->jit_module);
     dev->jit_module = mod;
     dev->jit_fn = fn;
-    dev->jit_key = key;
+    dev->jit_key = jc.key;
     // its resources, read now: once the counting variant (the same kernel name in another
     // module) is loaded, an attribute query of this function returned that one's scratch
     // size -- and a second renderer's counting module can do the same at load time, so
@@ -2207,7 +1881,7 @@ extern "C" int wo_dev_set_jit(WoDev* dev, const char* src, char* err, size_t err
     (void)hipFuncGetAttribute(&dev->jit_attr[2], HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn);
     {
         uint32_t group = 0, priv = 0;
-        if (kd_segment_sizes(code, "wo_jit_pathtrace", &group, &priv)) {
+        if (wojit::kd_segment_sizes(jc.code.data(), jc.code.size(), "wo_jit_pathtrace", &group, &priv)) {
             dev->jit_attr[0] = (int)priv;
             dev->jit_attr[2] = (int)group;
         }
@@ -2218,68 +1892,17 @@ extern "C" int wo_dev_set_jit(WoDev* dev, const char* src, char* err, size_t err
         const int v = m ? atoi(m + strlen("// wo_share_tiles ")) : 0;
         dev->jit_share_tiles = v >= 1 && v <= 64 ? (uint32_t)v : kShareTiles;
     }
-    dev->jit_origin = origin;
-    dev->jit_compile_sec = sec;
+    dev->jit_origin = jc.origin;
+    dev->jit_compile_sec = jc.seconds;
     return 0;
 }
 
-// ---- background compiles (wo_dev.h WoJitJob) ----
 extern "C" int wo_dev_jit_cached(WoDev* dev, const char* src) {
-    const std::string key = jit_key(src, dev->arch);
-    {
-        std::lock_guard<std::mutex> lock(g_jit_mu);
-        if (jit_cache().count(key)) return 1;
-    }
-    void* buf = nullptr;
-    size_t n = 0;
-    if (wo_jit_disk_load(key.c_str(), &buf, &n) != 0) return 0;
-    std::vector<char> code((char*)buf, (char*)buf + n);
-    free(buf);
-    std::lock_guard<std::mutex> lock(g_jit_mu);
-    jit_cache_put(key, code);
-    return 1;
+    std::vector<char> code;
+    return wojit::jit_lookup(wojit::jit_key(src, dev->arch), &code) >= 0 ? 1 : 0;
 }
 
-struct WoJitJob {
-    std::thread th;
-    std::atomic<int> done{0};
-    int rc = 0;
-    std::string src, arch;
-    char err[512] = {0};
-};
-
-extern "C" WoJitJob* wo_jit_job_start(WoDev* dev, const char* src) {
-    WoJitJob* j = new (std::nothrow) WoJitJob();
-    if (!j) return nullptr;
-    j->src = src;
-    j->arch = dev->arch;
-    try {
-        j->th = std::thread([j]() {
-            std::vector<char> code;
-            std::string key;
-            int origin = -1;
-            double sec = 0.0;
-            j->rc = jit_code(j->src.c_str(), j->arch, false, code, key, origin, sec, j->err, sizeof j->err);
-            j->done.store(1, std::memory_order_release);
-        });
-    } catch (...) {
-        delete j;
-        return nullptr;
-    }
-    return j;
-}
-
-extern "C" int wo_jit_job_done(WoJitJob* j) { return j->done.load(std::memory_order_acquire); }
-
-extern "C" const char* wo_jit_job_source(WoJitJob* j) { return j->src.c_str(); }
-
-extern "C" int wo_jit_job_finish(WoJitJob* j, char* err, size_t errlen) {
-    if (j->th.joinable()) j->th.join();
-    const int rc = j->rc;
-    if (rc && err && errlen) snprintf(err, errlen, "%s", j->err);
-    delete j;
-    return rc;
-}
+extern "C" WoJitJob* wo_jit_job_start(WoDev* dev, const char* src) { return wojit::jit_job_start(src, dev->arch); }
 
 extern "C" int wo_dev_jit_origin(WoDev* dev, double* seconds) {
     if (!dev || !dev->jit_fn) return -1;
@@ -2295,11 +1918,6 @@ extern "C" int wo_dev_lanes_info(WoDev* dev, uint32_t* out) {
     out[3] = dev->lbvh.always;
     out[4] = dev->ray_last ? dev->ray_kind : dev->last_kind;
     return 0;
-}
-
-extern "C" int wo_jit_compile_check(const char* src, const char* arch, char* err, size_t errlen) {
-    std::vector<char> code;
-    return jit_compile(src, arch ? std::string(arch) : std::string("gfx950"), false, code, err, errlen);
 }
 
 extern "C" int wo_dev_jit_active(WoDev* dev) { return dev && dev->jit_fn ? 1 : 0; }
@@ -2329,8 +1947,9 @@ static uint32_t shape_of(const char* f) {
 }
 static uint32_t tiles_across(uint32_t width, uint32_t shape) { return (width + (1u << (shape & 15u)) - 1u) >> (shape & 15u); }
 
+// *n_wg: the workgroups to launch, the big tiles and the small ones over the rows left
 static PathLaunch plan_tiles(uint32_t width, uint32_t rows, uint32_t resident, uint32_t band_rows,
-                             uint32_t want_per_wg) {
+                             uint32_t want_per_wg, uint64_t* n_wg) {
     const uint32_t s44 = 2u | (2u << 4);
     PathLaunch g = {};
     // the tail's tiles: 4x4 (2x2 / 4x2 for an 8-rank share's tail: within noise,
@@ -2395,7 +2014,19 @@ static PathLaunch plan_tiles(uint32_t width, uint32_t rows, uint32_t resident, u
     if (big == small) rows_big = ((rows + bh - 1u) / bh) * bh;  // one shape: the big grid covers everything
     g.rows_big = rows_big;
     g.n_big = g.tiles_x_big * (rows_big / bh);
+    *n_wg = g.n_big + (rows > rows_big ? (uint64_t)g.tiles_x_small * ((rows - rows_big + sh - 1u) / sh) : 0u);
     return g;
+}
+
+// The planner without a device (CPU tests): out = big_log2, small_log2, n_big,
+// tiles_x_big, tiles_x_small, rows_big, workgroups; -1 where launch_impl refuses the frame.
+extern "C" int wo_plan_tiles(uint32_t width, uint32_t rows, uint32_t resident, uint32_t band_rows,
+                             uint32_t want_per_wg, uint32_t out[7]) {
+    uint64_t n_wg = 0;
+    const PathLaunch g = plan_tiles(width, rows, resident, band_rows, want_per_wg, &n_wg);
+    const uint32_t v[7] = {g.big_log2, g.small_log2, g.n_big, g.tiles_x_big, g.tiles_x_small, g.rows_big, (uint32_t)n_wg};
+    memcpy(out, v, sizeof v);
+    return n_wg < (1ull << 31) ? 0 : -1;
 }
 
 static const size_t kLdsBudget = 64u * 1024u;
@@ -2447,10 +2078,8 @@ static bool is_lane_kind(PathKind kind) { return kind < kJit; }
 // out[1] = private bytes per lane, out[2] = registers (VGPRs), out[3] = static LDS
 // bytes.  A profile session records these beside its counters, so a summary says
 // which code object it measured.
-extern "C" int wo_dev_kernel_info(WoDev* dev, char* key_hex, uint32_t* out) {
-    if (!dev || !out || dev->last_kind == 0u) return -1;
+static int kernel_info_current(WoDev* dev, char* key_hex, uint32_t* out) {  // dev's device is current
     const PathKind kind = (PathKind)dev->last_kind;
-    if (hipSetDevice(dev->device) != hipSuccess) return -1;
     out[0] = (uint32_t)kind;
     if (kind == kJit) {
         if (!dev->jit_fn || dev->jit_attr[0] < 0 || dev->jit_attr[1] < 0 || dev->jit_attr[2] < 0) return -1;
@@ -2468,6 +2097,16 @@ extern "C" int wo_dev_kernel_info(WoDev* dev, char* key_hex, uint32_t* out) {
         if (key_hex) snprintf(key_hex, 65, "static:%u:%.40s", (unsigned)kind, WO_STATIC_SRC_SHA);
     }
     return 0;
+}
+
+// (the caller's current device is restored on every path, as renderer.c's multi-device entries do)
+extern "C" int wo_dev_kernel_info(WoDev* dev, char* key_hex, uint32_t* out) {
+    if (!dev || !out || dev->last_kind == 0u) return -1;
+    const int prev = wo_dev_current();
+    if (hipSetDevice(dev->device) != hipSuccess) return -1;
+    const int rc = kernel_info_current(dev, key_hex, out);
+    if (prev >= 0) (void)hipSetDevice(prev);
+    return rc;
 }
 
 static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* stream_v,
@@ -2583,18 +2222,14 @@ static int launch_impl(WoDev* dev, WoFrame const* frame_in, void* d_out, void* s
         if (e != hipSuccess || per_cu < 1) per_cu = 1;
         // a rank's local rows are bands of tile_rows consecutive frame rows: a tile
         // taller than a band would join rows far apart (incoherent primary rays)
+        uint64_t n_wg = 0;
         PathLaunch tg = plan_tiles(fr.width, local_rows, (uint32_t)dev->cus * (uint32_t)per_cu,
-                                   fr.nranks > 1u ? fr.tile_rows : ~0u, kind == kJit ? dev->jit_share_tiles : kShareTiles);
+                                   fr.nranks > 1u ? fr.tile_rows : ~0u, kind == kJit ? dev->jit_share_tiles : kShareTiles,
+                                   &n_wg);
         if (d_accum && fr.mode == WO_MODE_PATHTRACE) {
             tg.acc = d_accum;
             tg.acc_spp = accum_spp;
         }
-        const uint64_t n_small =
-            local_rows > tg.rows_big
-                ? (uint64_t)tg.tiles_x_small * ((local_rows - tg.rows_big + (1u << (tg.small_log2 >> 4)) - 1u) >>
-                                                (tg.small_log2 >> 4))
-                : 0u;
-        const uint64_t n_wg = (uint64_t)tg.n_big + n_small;
         if (n_wg >= (1ull << 31)) {
             snprintf(err, errlen, "frame too large (%llu workgroups)", (unsigned long long)n_wg);
             return -1;
@@ -2766,12 +2401,9 @@ extern "C" int wo_dev_count_work(WoDev* dev, WoFrame const* frame, unsigned long
         return -1;
     }
     if (dev->jit_fn && !dev->count_fn) {
-        std::vector<char> code;
-        std::string key;
-        int origin = -1;
-        double sec = 0.0;
-        if (jit_code(dev->jit_src.c_str(), dev->arch, true, code, key, origin, sec, err, errlen)) return -1;
-        if (load_jit_module(code, &dev->count_module, &dev->count_fn, err, errlen)) return -1;
+        wojit::JitCode jc;
+        if (wojit::jit_code(dev->jit_src.c_str(), dev->arch, true, &jc, err, errlen)) return -1;
+        if (load_jit_module(jc.code, &dev->count_module, &dev->count_fn, err, errlen)) return -1;
     }
     const size_t local_rows = wo_rank_local_rows_ex(fr.height, fr.tile_rows, fr.nranks, fr.band_cycle, fr.band_skip);
     if (ensure_buffer(&dev->d_frame, &dev->frame_cap, local_rows * fr.width * sizeof(float4), err, errlen)) return -1;

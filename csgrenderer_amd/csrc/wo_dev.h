@@ -43,7 +43,7 @@ void wo_dev_destroy(WoDev* dev);
 /* Copy the compiled scene to HBM (blocking). */
 int wo_dev_upload_scene(WoDev* dev, WoRec const* prog, uint32_t n_recs, uint32_t n_prims,
                         WoMaterial const* mats, uint32_t n_mats, char* err, size_t errlen);
-/* Compile (hiprtc, cached per process) and load a scene-specialised path
+/* Compile (jit_code.cpp: hiprtc, cached per process and on disk) and load a scene-specialised path
  * tracer from `src` (scene_jit.c); NULL unloads it.  While loaded, PATHTRACE and
  * NORMALS frames launch it instead of the interpreter kernel. */
 int wo_dev_set_jit(WoDev* dev, const char* src, char* err, size_t errlen);
@@ -159,6 +159,13 @@ int wo_dev_lanes_info(WoDev* dev, uint32_t* out);
 int wo_lane_bvh_build(WoRec const* prog, uint32_t n_recs, uint32_t n_prims, WoMaterial const* mats, uint32_t n_mats,
                       WoLaneBvhDesc* desc, uint32_t info[3], void* blob, size_t cap, size_t* size, char* err,
                       size_t errlen);
+/* trace_kernels.hip plan_tiles: the path tracer's launch grid for `rows` local rows of
+ * `width` pixels, without a device: out = big_log2, small_log2 (a tile shape: log2 width |
+ * log2 height << 4), n_big, tiles_x_big, tiles_x_small, rows_big (PathLaunch) and the
+ * workgroups launched.  `resident`: workgroups the device holds at once; `band_rows`: rows
+ * of a rank's band (~0u: one rank); -1 when the grid is too large to launch. */
+int wo_plan_tiles(uint32_t width, uint32_t rows, uint32_t resident, uint32_t band_rows, uint32_t want_per_wg,
+                  uint32_t out[7]);
 /* the last launch's path kernel: key (65 B), out[4] = kind, scratch B/lane, VGPRs, LDS */
 int wo_dev_kernel_info(WoDev* dev, char* key_hex, uint32_t* out);
 /* Wait for the slot's frame; *host = its pixels (RGBA float; NULL when the

@@ -668,6 +668,29 @@ def lane_bvh(prog, n_recs: int, n_prims: int, mats, n_mats: int):
     return desc, blob.raw[:size.value], int(info[0]), (int(info[1]), int(info[2]))
 
 
+PLAN_FIELDS = ("big_log2", "small_log2", "n_big", "tiles_x_big", "tiles_x_small", "rows_big", "workgroups")
+
+
+def plan_tiles(width: int, rows: int, resident: int, band_rows: int = 0xFFFFFFFF, want_per_wg: int = 3):
+    """The path tracer's launch grid for `rows` local rows of `width` pixels (csrc/wo_dev.h
+    wo_plan_tiles; no GPU needed): the PLAN_FIELDS values, or None for a grid too large to launch."""
+    plan = load().wo_plan_tiles
+    plan.argtypes = [c_uint32] * 5 + [POINTER(c_uint32)]
+    out = (c_uint32 * 7)()
+    return None if plan(width, rows, resident, band_rows, want_per_wg, out) else tuple(int(v) for v in out)
+
+
+def current_device() -> int:
+    """The calling thread's current HIP device (csrc/wo_dev.h wo_dev_current), or -1."""
+    return int(load().wo_dev_current())
+
+
+def select_device(device: int):
+    """Make `device` the calling thread's current HIP device (csrc/wo_dev.h wo_dev_select)."""
+    if load().wo_dev_select(c_int(device)) != 0:
+        raise WololoError(f"cannot select HIP device {device}")
+
+
 BAND_CYCLE_MAX = 65536  # wo_scene.h WO_BAND_CYCLE_MAX
 
 

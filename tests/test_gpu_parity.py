@@ -610,6 +610,25 @@ def test_kernel_info_names_the_code_object():
         x.close()
 
 
+def test_kernel_info_keeps_the_callers_device():
+    """wo_renderer_kernel_info selects the renderer's device for its query and restores
+    the caller's: a renderer on device 1 queried while device 0 is current leaves
+    device 0 current (bench.py reports kernel_info while it holds several devices)."""
+    if wl.load().wo_hip_device_count() < 2:
+        pytest.skip("needs two HIP devices")
+    wl.select_device(1)
+    try:
+        r, info = _scene("csg32", "auto")
+        assert r.lib.wo_renderer_device(r.ptr) == 1
+        r.render(info.params(width=16, height=8, spp=1))
+        wl.select_device(0)
+        assert r.kernel_info() is not None
+        assert wl.current_device() == 0
+        r.close()
+    finally:
+        wl.select_device(0)
+
+
 @pytest.mark.parametrize("window", ["lds2", "default"])
 def test_jit_event_windows(window, monkeypatch):
     """The specialised kernel's event windows -- the sorted LDS list (csg32_nested),

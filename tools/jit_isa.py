@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--src", default=None, help="compile this (edited) generated source instead of the scene's")
     ap.add_argument("--dump", default=None, help="write the scene's generated source here")
     ap.add_argument("--rtc", action="store_true",
-                    help="compile through hiprtc with the runtime's options (trace_kernels.hip jit_options) "
+                    help="compile through hiprtc with the runtime's options (jit_code.cpp jit_options) "
                          "and read the code object's resource notes, instead of hipcc -S")
     a = ap.parse_args()
     from csgrenderer_amd import scenes
@@ -71,7 +71,7 @@ def main():
 
 
 def rtc(src, defs, keep):
-    """hiprtc compile as jit_compile does (same embedded headers and options)."""
+    """hiprtc compile as jit_code.cpp does (same embedded headers and options)."""
     import ctypes
     lib = ctypes.CDLL("/opt/rocm/lib/libhiprtc.so")
     hdrs = [open(os.path.join(ROOT, "csgrenderer_amd/csrc/wo_device_common.h"), "rb").read(),
