@@ -40,6 +40,9 @@ static const AbiField kAbi[] = {
     T(Wo_Ray), F(Wo_Ray, origin), F(Wo_Ray, t_max), F(Wo_Ray, dir), F(Wo_Ray, reserved),
     T(Wo_RayHit), F(Wo_RayHit, t), F(Wo_RayHit, flags), F(Wo_RayHit, leaf), F(Wo_RayHit, node),
     F(Wo_RayHit, normal), F(Wo_RayHit, material),
+    T(Wo_RayCrossing), F(Wo_RayCrossing, t), F(Wo_RayCrossing, flags), F(Wo_RayCrossing, leaf),
+    F(Wo_RayCrossing, node),
+    T(Wo_RaySpans), F(Wo_RaySpans, count), F(Wo_RaySpans, flags), F(Wo_RaySpans, length), F(Wo_RaySpans, stored),
 };
 
 #undef T

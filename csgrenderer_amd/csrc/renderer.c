@@ -814,6 +814,75 @@ int wo_renderer_trace_rays(Wo_Renderer* r, Wo_Ray const* rays, Wo_RayHit* hits, 
     return 0;
 }
 
+/* the span kernel writes a summary and a crossing as one 16-byte row each */
+_Static_assert(sizeof(Wo_RaySpans) == 16 && sizeof(Wo_RayCrossing) == 16, "Wo_RaySpans / Wo_RayCrossing are 16 bytes");
+
+int wo_renderer_trace_spans_device(Wo_Renderer* r, Wo_Ray const* d_rays, Wo_RaySpans* d_spans,
+                                   Wo_RayCrossing* d_crossings, size_t n, uint32_t max_crossings, void* stream) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    if (n == 0) return 0;
+    if (!d_rays || !d_spans || (max_crossings != 0u && !d_crossings)) {
+        wo_set_error("trace_spans: NULL ray, span or crossing buffer");
+        return -1;
+    }
+    char err[256] = {0};
+    if (wo_dev_trace_spans(r->dev, d_rays, d_spans, d_crossings, n, max_crossings, stream, err, sizeof err)) {
+        wo_set_error("span launch failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_trace_spans(Wo_Renderer* r, Wo_Ray const* rays, Wo_RaySpans* spans, Wo_RayCrossing* crossings, size_t n,
+                            uint32_t max_crossings) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    if (n == 0) return 0;
+    if (!rays || !spans || (max_crossings != 0u && !crossings)) {
+        wo_set_error("trace_spans: NULL ray, span or crossing buffer");
+        return -1;
+    }
+    char err[256] = {0};
+    if (wo_dev_trace_spans_host(r->dev, rays, spans, crossings, n, max_crossings, err, sizeof err)) {
+        wo_set_error("span query failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_classify_points_device(Wo_Renderer* r, float const* d_points, uint32_t* d_out, size_t n, void* stream) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    if (n == 0) return 0;
+    if (!d_points || !d_out) {
+        wo_set_error("classify_points: NULL point or result buffer");
+        return -1;
+    }
+    char err[256] = {0};
+    if (wo_dev_classify_points(r->dev, d_points, d_out, n, stream, err, sizeof err)) {
+        wo_set_error("point launch failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_classify_points(Wo_Renderer* r, float const* points, uint32_t* out, size_t n) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    if (n == 0) return 0;
+    if (!points || !out) {
+        wo_set_error("classify_points: NULL point or result buffer");
+        return -1;
+    }
+    char err[256] = {0};
+    if (wo_dev_classify_points_host(r->dev, points, out, n, err, sizeof err)) {
+        wo_set_error("point query failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
 /* oracle.c normalize3 / sqrt_pt, one rounding per operation (-ffp-contract=off) */
 static void normalize3f(float v[3]) {
     const float dot = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];

@@ -144,21 +144,20 @@ struct InterpTracer {
 
     __device__ __forceinline__ WoRec hit_leaf(const Hit& h) const { return prog[ordpc[h.ord()] + 1u + h.member()]; }
 
-    // Nearest change of the root's membership after WO_T_MIN along o + t d.
-    __device__ __forceinline__ bool trace(F3 o, F3 d, Hit& hit) {
+    // Pass 1: walk the program, cull, intersect, collect the events after WO_T_MIN into
+    // `win` (a cleared window of any size).  Leaves the compacted program, the ordinal ->
+    // pc map and the membership bits at t_min behind; returns the bit stack, whose low
+    // bit is the root's value at t_min.
+    template <class Win>
+    __device__ __forceinline__ uint32_t collect(F3 o, F3 d, Win& win, F3& inv, bool& have_inv) {
         const float tmin = WO_T_MIN;
-        Window win;
-        win.clear();
         bits = 0;
         ncodes = 0;
         nprims = 0;
         uint32_t code_acc = 0;
         uint32_t hib_acc = 0;
         uint32_t st = 0;  // bit stack: the root value at t_min, evaluated on the way
-        F3 inv = f3(0.0f, 0.0f, 0.0f);
-        bool have_inv = false;
 
-        // pass 1: walk the program, cull, intersect, collect events
         uint32_t pc = 0;
         while (pc < nrec) {
             WoRec rec = prog[pc];
@@ -221,6 +220,55 @@ struct InterpTracer {
         }
         if (ncodes & 7u) codes[ncodes >> 3] = code_acc;
         if (nprims > 64u && ((nprims - 64u) & 31u)) hib[((nprims - 64u) >> 5) * 64u + lane] = hib_acc;
+        return st;
+    }
+
+    // The window ran empty but had dropped events: re-collect the events strictly
+    // after `key` (the membership state carries on).
+    template <class Win>
+    __device__ __forceinline__ void recollect(F3 o, F3 d, uint64_t key, Win& win, F3& inv, bool& have_inv) {
+        const float tmin = WO_T_MIN;
+        WO_WK(WO_WORK_RECOLLECTS);
+        win.clear();
+        uint32_t ordc = 0;
+        uint32_t nwords = (ncodes + 7u) >> 3;
+        for (uint32_t w = 0; w < nwords; ++w) {
+            uint32_t word = uni(codes[w]);
+            uint32_t n = ncodes - w * 8u;
+            n = n < 8u ? n : 8u;
+            for (uint32_t j = 0; j < n; ++j) {
+                if (((word >> (4u * j)) & 15u) != kCodePrim) continue;
+                uint32_t ppc = uni(ordpc[ordc]);
+                uint32_t count = uni(prog[ppc].u0);
+                Ivl iv = prim_interval<kCount>(prog, ppc, count, o, d, inv, have_inv, wk);
+                if (!(iv.a > iv.b)) {
+                    if (iv.a > tmin) {
+                        uint64_t k2 = event_key(iv.a, ordc, 0u, iv.ma);
+                        if (k2 > key) {
+                            WO_WK(WO_WORK_EVENTS);
+                            win.insert(k2);
+                        }
+                    }
+                    if (iv.b > tmin && iv.b < kInf) {
+                        uint64_t k2 = event_key(iv.b, ordc, 1u, iv.mb);
+                        if (k2 > key) {
+                            WO_WK(WO_WORK_EVENTS);
+                            win.insert(k2);
+                        }
+                    }
+                }
+                ++ordc;
+            }
+        }
+    }
+
+    // Nearest change of the root's membership after WO_T_MIN along o + t d.
+    __device__ __forceinline__ bool trace(F3 o, F3 d, Hit& hit) {
+        Window win;
+        win.clear();
+        F3 inv = f3(0.0f, 0.0f, 0.0f);
+        bool have_inv = false;
+        const uint32_t st = collect(o, d, win, inv, have_inv);
 
         // pass 2: sweep events in key order; the first root flip is the hit
         if (win.empty()) return false;
@@ -236,42 +284,7 @@ struct InterpTracer {
                 return true;
             }
             root = r;
-            if (win.empty() && win.dropped()) {
-                // window exhausted but events were dropped: re-collect the events
-                // strictly after `key` (the membership state carries on)
-                WO_WK(WO_WORK_RECOLLECTS);
-                win.clear();
-                uint32_t ordc = 0;
-                uint32_t nwords = (ncodes + 7u) >> 3;
-                for (uint32_t w = 0; w < nwords; ++w) {
-                    uint32_t word = uni(codes[w]);
-                    uint32_t n = ncodes - w * 8u;
-                    n = n < 8u ? n : 8u;
-                    for (uint32_t j = 0; j < n; ++j) {
-                        if (((word >> (4u * j)) & 15u) != kCodePrim) continue;
-                        uint32_t ppc = uni(ordpc[ordc]);
-                        uint32_t count = uni(prog[ppc].u0);
-                        Ivl iv = prim_interval<kCount>(prog, ppc, count, o, d, inv, have_inv, wk);
-                        if (!(iv.a > iv.b)) {
-                            if (iv.a > tmin) {
-                                uint64_t k2 = event_key(iv.a, ordc, 0u, iv.ma);
-                                if (k2 > key) {
-                                    WO_WK(WO_WORK_EVENTS);
-                                    win.insert(k2);
-                                }
-                            }
-                            if (iv.b > tmin && iv.b < kInf) {
-                                uint64_t k2 = event_key(iv.b, ordc, 1u, iv.mb);
-                                if (k2 > key) {
-                                    WO_WK(WO_WORK_EVENTS);
-                                    win.insert(k2);
-                                }
-                            }
-                        }
-                        ++ordc;
-                    }
-                }
-            }
+            if (win.empty() && win.dropped()) recollect(o, d, key, win, inv, have_inv);
         }
         return false;
     }
@@ -1358,6 +1371,247 @@ __global__ __launch_bounds__(kBlock, kMode == 2 ? WO_LANES_BVH_MIN_WAVES : WO_LA
     }
 }
 
+// ---------------------------------------------------------------------------
+// Ray span queries (wo_renderer_trace_spans_device): the interpreter's sweep carried
+// on past the first flip of the root.  Every flip in (WO_T_MIN, t_max] is a crossing;
+// a ray's summary is Wo_RaySpans (count, flags, length, stored: one uint4), a crossing
+// Wo_RayCrossing (t, flags, leaf, node: one float4), stored crossing-major
+// (crossing k of ray i at [k * n + i]: a wave's k-th store is 64 consecutive rows).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kRayInside = 16u, kRayTruncated = 32u;  // WO_RAY_INSIDE, WO_RAY_TRUNCATED
+
+// Window's sorted network at another size (Window itself is the specialised kernels'
+// too and stays as it is): the kN nearest events, the largest dropped on overflow.
+template <int kN>
+struct SpanWindow {
+    static_assert(WO_WIN_F64, "the network is Window's v_min_f64 / v_max_f64 one");
+    static constexpr uint64_t kEmpty = Window::kEmpty;
+    uint64_t k[kN];
+    uint32_t n;  // inserts since clear()
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int i = 0; i < kN; ++i) k[i] = kEmpty;
+        n = 0;
+    }
+    __device__ __forceinline__ bool dropped() const { return n > (uint32_t)kN; }
+    __device__ __forceinline__ bool empty() const { return k[0] == kEmpty; }
+    __device__ __forceinline__ void insert(uint64_t key) {
+        ++n;
+#pragma unroll
+        for (int i = kN - 1; i > 0; --i) k[i] = key_max(k[i - 1], key_min(key, k[i]));
+        k[0] = key_min(key, k[0]);
+    }
+    __device__ __forceinline__ uint64_t pop() {
+        uint64_t r = k[0];
+#pragma unroll
+        for (int i = 0; i < kN - 1; ++i) k[i] = k[i + 1];
+        k[kN - 1] = kEmpty;
+        return r;
+    }
+};
+
+struct SpanBatch {
+    const float4* __restrict__ rays;
+    uint4* __restrict__ spans;
+    float4* __restrict__ crossings;      // [max_crossings][n], or null when max_crossings = 0
+    const uint32_t* __restrict__ nodes;  // per program record: its source node handle
+    uint64_t n;
+    uint32_t max_crossings;
+};
+
+// A ray's sweep state: what Wo_RaySpans reports, in the making.
+struct SpanSum {
+    uint32_t count;
+    uint32_t inside0;  // the root's value at WO_T_MIN
+    uint32_t root;     // the root's value after the last swept event
+    float len, t_in;
+};
+
+// The interpreter's trace as a span query.  Pass 1 is trace()'s.  Pass 2 sweeps the
+// events in key order and calls crossing(key, root_after, k) at the k-th flip of the
+// root instead of returning at the first one; it re-collects strictly after the last
+// swept key whenever the window ran empty after dropping events.  An event later than
+// t_max ends the sweep (no later event can be a crossing).
+// Termination: a re-collect admits only keys greater than the last swept one, each
+// window holds at least one of them, and a ray has at most two events per primitive;
+// so every key is swept at most once and the loop needs no iteration cap.
+// The result does not depend on kN: the windows only batch one sorted sequence.
+template <int kN, class Crossing>
+__device__ __forceinline__ SpanSum trace_spans(InterpTracer<false>& tr, F3 o, F3 d, float t_max, Crossing&& crossing) {
+    SpanWindow<kN> win;
+    win.clear();
+    F3 inv = f3(0.0f, 0.0f, 0.0f);
+    bool have_inv = false;
+    SpanSum s;
+    s.root = s.inside0 = tr.collect(o, d, win, inv, have_inv) & 1u;
+    s.count = 0;
+    s.len = 0.0f;
+    s.t_in = WO_T_MIN;
+    while (!win.empty()) {
+        const uint64_t key = win.pop();
+        const float t = __uint_as_float((uint32_t)(key >> 32));
+        if (t > t_max) break;
+        tr.toggle(key_ord(key));
+        const uint32_t r = tr.eval_root();
+        if (r != s.root) {
+            crossing(key, r, s.count);
+            ++s.count;
+            // fp32, one rounding per operation, in sweep order (Wo_RaySpans.length)
+            if (r)
+                s.t_in = t;
+            else
+                s.len = s.len + (t - s.t_in);
+            s.root = r;
+        }
+        if (win.empty() && win.dropped()) tr.recollect(o, d, key, win, inv, have_inv);
+    }
+    if (s.root && t_max > s.t_in) s.len = s.len + (t_max - s.t_in);
+    return s;
+}
+
+// One ray per lane, the grid and LDS layout of trace_rays_kernel; lanes past n and
+// lanes with an invalid ray sweep a copy of the wave's first valid ray (t_max too)
+// and drop the result.
+template <bool kProgInLds, int kN>
+__global__ __launch_bounds__(kBlock) void trace_spans_kernel(const WoRec* __restrict__ gprog, uint32_t nrec,
+                                                             KLayout lay, SpanBatch sb) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uni(tid >> 6);
+
+    uint32_t* scratch = smem;
+    InterpTracer<false> tr;
+    if constexpr (kProgInLds) {
+        const uint4* src = reinterpret_cast<const uint4*>(gprog);
+        uint4* dst = reinterpret_cast<uint4*>(smem);
+        for (uint32_t i = tid; i < nrec * 2u; i += kBlock) dst[i] = src[i];
+        __syncthreads();
+        tr.prog.p = reinterpret_cast<const WoRec*>(smem);
+        scratch = smem + nrec * 8u;
+    } else {
+        tr.prog.p = gprog;
+    }
+    uint32_t* ws = scratch + wave * lay.wave_words;
+    tr.nrec = nrec;
+    tr.codes = ws;
+    tr.ordpc = ws + lay.ordpc_off;
+    tr.hib = ws + lay.hib_off;
+    tr.lane = lane;
+
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t base = (uint64_t)blockIdx.x * kBlock + wave * 64u; base < sb.n; base += stride) {
+        const uint64_t i = base + lane;
+        const bool in = i < sb.n;
+        float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+        if (in) {
+            r0 = sb.rays[2u * i];
+            r1 = sb.rays[2u * i + 1u];
+        }
+        const bool valid = in && ray_valid(r0, r1);
+        const uint64_t vm = __ballot(valid);
+        SpanSum s;
+        s.count = 0;
+        s.inside0 = s.root = 0;
+        s.len = 0.0f;
+        s.t_in = WO_T_MIN;
+        if (vm != 0ull) {
+            const int src = __builtin_ctzll(vm);
+            auto from = [&](float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), src)); };
+            const F3 so = f3(from(r0.x), from(r0.y), from(r0.z)), sd = f3(from(r1.x), from(r1.y), from(r1.z));
+            const float st_max = from(r0.w);
+            const F3 to = valid ? f3(r0.x, r0.y, r0.z) : so, td = valid ? f3(r1.x, r1.y, r1.z) : sd;
+            s = trace_spans<kN>(tr, to, td, valid ? r0.w : st_max, [&](uint64_t key, uint32_t root_after, uint32_t k) {
+                if (!valid || k >= sb.max_crossings) return;
+                const uint32_t lo = (uint32_t)key;
+                const uint32_t leaf = tr.ordpc[lo >> 12] + 1u + (lo & 2047u);
+                const uint32_t flags = kRayHit | ((lo & kKeyTypeBit) ? kRayExit : 0u) | (root_after ? kRayEnters : 0u);
+                sb.crossings[(uint64_t)k * sb.n + i] =
+                    make_float4(__uint_as_float((uint32_t)(key >> 32)), __uint_as_float(flags), __uint_as_float(leaf),
+                                __uint_as_float(sb.nodes[leaf]));
+            });
+        }
+        if (in) {
+            uint4 out = make_uint4(0u, kRayInvalid, 0u, 0u);
+            if (valid) {
+                const uint32_t stored = s.count < sb.max_crossings ? s.count : sb.max_crossings;
+                const uint32_t flags = (s.inside0 ? kRayInside : 0u) | (s.count > stored ? kRayTruncated : 0u);
+                out = make_uint4(s.count, flags, __float_as_uint(s.len), stored);
+            }
+            sb.spans[i] = out;
+        }
+    }
+}
+
+// Point membership classification (wo_renderer_classify_points_device): one point
+// (a float4, w ignored) per lane, the program walked once by the wave, the root
+// evaluated on pass 1's bit stack.  Each leaf in fp32, one rounding per operation:
+// sphere ((gx gx + gy gy) + gz gz) <= r^2 with g = p - c, half-space
+// ((nx px + ny py) + nz pz) <= h; a primitive is the AND of its members.
+// BOUND records are stepped over, never used to skip a subtree: skipping needs a
+// margin by which every leaf test under the BOUND provably fails, and a BOUND taken
+// from a polytope of half-spaces (scene_compile.c polytope_bound) gives none -- a point
+// outside the bounding sphere by g may violate each plane near a sharp vertex by
+// far less than g, down to the rounding of the plane test.  So the result is the
+// evaluation that ignores BOUNDs by construction.
+constexpr uint32_t kPointInside = 1u, kPointInvalid = 8u;  // WO_POINT_* (renderer_ext.h)
+
+template <bool kProgInLds>
+__global__ __launch_bounds__(kBlock) void classify_points_kernel(const WoRec* __restrict__ gprog, uint32_t nrec,
+                                                                 const float4* __restrict__ points,
+                                                                 uint32_t* __restrict__ out, uint64_t n) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    ProgPtr prog;
+    if constexpr (kProgInLds) {
+        const uint4* src = reinterpret_cast<const uint4*>(gprog);
+        uint4* dst = reinterpret_cast<uint4*>(smem);
+        for (uint32_t i = threadIdx.x; i < nrec * 2u; i += kBlock) dst[i] = src[i];
+        __syncthreads();
+        prog.p = reinterpret_cast<const WoRec*>(smem);
+    } else {
+        prog.p = gprog;
+    }
+    constexpr uint32_t kTruth = InterpTracer<false>::kTruth;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    // (every lane of a wave runs the same trips: the bound is the wave's, the walk wave-uniform)
+    for (uint64_t base = (uint64_t)blockIdx.x * kBlock + (threadIdx.x & ~63u); base < n; base += stride) {
+        const uint64_t i = base + (threadIdx.x & 63u);
+        const bool in = i < n;
+        const float4 p = in ? points[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        uint32_t st = 0;
+        uint32_t pc = 0;
+        while (pc < nrec) {
+            const WoRec rec = prog[pc];
+            const uint32_t op = uni(rec.op);
+            if (op == WO_OP_BOUND) {
+                ++pc;
+            } else if (op == WO_OP_PRIM) {
+                const uint32_t count = uni(rec.u0);
+                bool inside = true;
+                for (uint32_t m = 0; m < count; ++m) {
+                    const WoRec L = prog[pc + 1u + m];
+                    float v;
+                    if (uni(L.op) == WO_LEAF_SPHERE) {
+                        const float gx = p.x - L.f[0], gy = p.y - L.f[1], gz = p.z - L.f[2];
+                        v = (gx * gx + gy * gy) + gz * gz;
+                    } else {
+                        v = (L.f[0] * p.x + L.f[1] * p.y) + L.f[2] * p.z;
+                    }
+                    inside = inside & (v <= L.f[3]);
+                }
+                st = (st << 1) | (inside ? 1u : 0u);
+                pc += 1u + count;
+            } else {
+                const uint32_t tt = (kTruth >> (4u * op)) & 15u;
+                st = ((st >> 2) << 1) | ((tt >> (st & 3u)) & 1u);
+                ++pc;
+            }
+        }
+        if (in) {
+            const bool fin = (fabsf(p.x) < kInf) & (fabsf(p.y) < kInf) & (fabsf(p.z) < kInf);
+            out[i] = fin ? ((st & 1u) ? kPointInside : 0u) : kPointInvalid;
+        }
+    }
+}
+
 // Sums (and clears) the segment slots into the caller's counter.
 __global__ __launch_bounds__(kBlock) void seg_collect_kernel(unsigned long long* __restrict__ slots,
                                                              unsigned long long* __restrict__ counter) {
@@ -2071,6 +2325,18 @@ static const void* ray_kernel(PathKind kind) {
     default: return nullptr;
     }
 }
+// a span launch's kernel: the program in LDS or not, the sweep's window 4, 8 or 16 keys wide
+template <bool kProgInLds>
+static const void* span_kernel_of(int window) {
+    switch (window) {
+    case 4: return (const void*)trace_spans_kernel<kProgInLds, 4>;
+    case 8: return (const void*)trace_spans_kernel<kProgInLds, 8>;
+    default: return (const void*)trace_spans_kernel<kProgInLds, 16>;
+    }
+}
+static const void* span_kernel(PathKind kind, int window) {
+    return kind == kInterpLds ? span_kernel_of<true>(window) : span_kernel_of<false>(window);
+}
 static bool is_lane_kind(PathKind kind) { return kind < kJit; }
 
 // The path kernel of the last launch: key_hex (65 bytes) gets the specialised
@@ -2380,6 +2646,174 @@ extern "C" int wo_dev_trace_rays_host(WoDev* dev, void const* rays, void* hits, 
     if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
     if (e != hipSuccess) {
         set_err(err, errlen, "ray query", e);
+        return -1;
+    }
+    return 0;
+}
+
+// ---- ray span queries and point classification ----
+
+// The span sweep's window (SpanWindow): 16 keys, one re-collect pass per 16 events
+// (1080p batches, tools/ray_span_bench.py, window 4 / 8 / 16: csg32_nested pixel rays
+// 0.461 / 0.403 / 0.358 ms, through rays csg256_chain 3.22 / 3.22 / 2.86 and rtiow_cover
+// 1.28 / 1.15 / 1.12; csg32 pixel rays, one or two events each, 0.113 / 0.118 / 0.121).
+// WOLOLO_SPAN_WINDOW = 4 | 8 | 16 (measurement) picks another; the results do not
+// depend on it.
+static int span_window() {
+    const char* w = getenv("WOLOLO_SPAN_WINDOW");
+    const int v = w && *w ? atoi(w) : 16;
+    return v == 4 || v == 8 ? v : 16;
+}
+
+extern "C" int wo_dev_trace_spans(WoDev* dev, void const* d_rays, void* d_spans, void* d_crossings, size_t n,
+                                  uint32_t max_crossings, void* stream_v, char* err, size_t errlen) {
+    hipStream_t stream = (hipStream_t)stream_v;  // NULL = the null stream (HIP convention)
+    if (n == 0) return 0;
+    if (!dev->d_prog || !dev->d_nodes || dev->n_nodes != dev->n_recs) {
+        snprintf(err, errlen, "no scene (or no node table) on the device");
+        return -1;
+    }
+    if (max_crossings != 0u && !d_crossings) {
+        snprintf(err, errlen, "NULL crossing buffer with max_crossings = %u", max_crossings);
+        return -1;
+    }
+    if (((uintptr_t)d_rays | (uintptr_t)d_spans | (uintptr_t)d_crossings) & 15u) {
+        snprintf(err, errlen, "ray, span and crossing buffers must be 16-byte aligned");
+        return -1;
+    }
+    if (dev->n_prims >= (1u << 20)) {
+        snprintf(err, errlen, "scene has %u primitives (max %u)", dev->n_prims, (1u << 20) - 1u);
+        return -1;
+    }
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    SpanBatch sb;
+    sb.rays = (const float4*)d_rays;
+    sb.spans = (uint4*)d_spans;
+    sb.crossings = max_crossings ? (float4*)d_crossings : nullptr;
+    sb.nodes = dev->d_nodes;
+    sb.n = n;
+    sb.max_crossings = max_crossings;
+    PathKind kind;
+    size_t dyn_lds = 0;
+    KLayout lay = {};
+    if (interp_plan(dev->n_recs, dev->n_prims, &lay, &kind, &dyn_lds, err, errlen)) return -1;
+    const void* kernel = span_kernel(kind, span_window());
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, dyn_lds);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    void* args[] = {&dev->d_prog, &dev->n_recs, &lay, &sb};
+    (void)hipLaunchKernel(kernel, dim3(ray_grid(dev, n, per_cu)), dim3(kBlock), args, dyn_lds, stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err(err, errlen, "span kernel launch", e);
+        return -1;
+    }
+    dev->ray_kind = (uint32_t)kind;
+    dev->ray_last = true;
+    return 0;
+}
+
+extern "C" int wo_dev_trace_spans_host(WoDev* dev, void const* rays, void* spans, void* crossings, size_t n,
+                                       uint32_t max_crossings, char* err, size_t errlen) {
+    if (n == 0) return 0;
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    // rays (2 rows each), then the summaries (1 row), then the crossings (max_crossings rows)
+    const size_t cross_rows = n * (size_t)max_crossings;
+    if (ensure_buffer(&dev->d_rayio, &dev->rayio_cap, (3u * n + cross_rows) * sizeof(float4), err, errlen)) return -1;
+    float4* d_rays = dev->d_rayio;
+    float4* d_spans = d_rays + 2u * n;
+    float4* d_cross = d_spans + n;
+    e = hipMemcpyAsync(d_rays, rays, 2u * n * sizeof(float4), hipMemcpyHostToDevice, dev->stream);
+    // the caller's crossing rows go up first: rows the query does not write come back as they were
+    if (e == hipSuccess && cross_rows)
+        e = hipMemcpyAsync(d_cross, crossings, cross_rows * sizeof(float4), hipMemcpyHostToDevice, dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipMemcpy(rays)", e);
+        return -1;
+    }
+    if (wo_dev_trace_spans(dev, d_rays, d_spans, cross_rows ? d_cross : nullptr, n, max_crossings, dev->stream, err,
+                           errlen))
+        return -1;
+    e = hipMemcpyAsync(spans, d_spans, n * sizeof(float4), hipMemcpyDeviceToHost, dev->stream);
+    if (e == hipSuccess && cross_rows)
+        e = hipMemcpyAsync(crossings, d_cross, cross_rows * sizeof(float4), hipMemcpyDeviceToHost, dev->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "span query", e);
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int wo_dev_classify_points(WoDev* dev, void const* d_points, void* d_out, size_t n, void* stream_v,
+                                      char* err, size_t errlen) {
+    hipStream_t stream = (hipStream_t)stream_v;  // NULL = the null stream (HIP convention)
+    if (n == 0) return 0;
+    if (!dev->d_prog) {
+        snprintf(err, errlen, "no scene on the device");
+        return -1;
+    }
+    if (((uintptr_t)d_points & 15u) || ((uintptr_t)d_out & 3u)) {
+        snprintf(err, errlen, "the point buffer must be 16-byte aligned (the result buffer 4-byte)");
+        return -1;
+    }
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    // the program in LDS where it fits (the kernel keeps no per-wave scratch)
+    const size_t prog_bytes = (size_t)dev->n_recs * sizeof(WoRec);
+    const bool in_lds = prog_bytes <= kLdsBudget;
+    const size_t dyn_lds = in_lds ? prog_bytes : 0;
+    const void* kernel =
+        in_lds ? (const void*)classify_points_kernel<true> : (const void*)classify_points_kernel<false>;
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, dyn_lds);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    const float4* pts = (const float4*)d_points;
+    uint32_t* out = (uint32_t*)d_out;
+    uint64_t n64 = n;
+    void* args[] = {&dev->d_prog, &dev->n_recs, &pts, &out, &n64};
+    (void)hipLaunchKernel(kernel, dim3(ray_grid(dev, n, per_cu)), dim3(kBlock), args, dyn_lds, stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err(err, errlen, "point kernel launch", e);
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int wo_dev_classify_points_host(WoDev* dev, void const* points, void* out, size_t n, char* err,
+                                           size_t errlen) {
+    if (n == 0) return 0;
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    // the points (one row each), then one word per point
+    if (ensure_buffer(&dev->d_rayio, &dev->rayio_cap, n * (sizeof(float4) + sizeof(uint32_t)), err, errlen)) return -1;
+    float4* d_points = dev->d_rayio;
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(d_points + n);
+    e = hipMemcpyAsync(d_points, points, n * sizeof(float4), hipMemcpyHostToDevice, dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipMemcpy(points)", e);
+        return -1;
+    }
+    if (wo_dev_classify_points(dev, d_points, d_out, n, dev->stream, err, errlen)) return -1;
+    e = hipMemcpyAsync(out, d_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, dev->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "point query", e);
         return -1;
     }
     return 0;

@@ -84,6 +84,22 @@ int wo_dev_trace_rays(WoDev* dev, void const* d_rays, void* d_hits, size_t n, in
 /* The same from and to host memory, through the device's own buffer and stream
  * (synchronous). */
 int wo_dev_trace_rays_host(WoDev* dev, void const* rays, void* hits, size_t n, int form, char* err, size_t errlen);
+/* Ray span queries (renderer_ext.h wo_renderer_trace_spans_device): n Wo_Ray at d_rays
+ * -> n Wo_RaySpans at d_spans and, crossing-major, up to max_crossings Wo_RayCrossing
+ * per ray at d_crossings (device memory, 16-byte aligned; d_crossings may be NULL when
+ * max_crossings is 0), async on `stream`.  Always the interpreter's sweep. */
+int wo_dev_trace_spans(WoDev* dev, void const* d_rays, void* d_spans, void* d_crossings, size_t n,
+                       uint32_t max_crossings, void* stream, char* err, size_t errlen);
+/* The same from and to host memory (synchronous).  The caller's crossing rows are
+ * uploaded first, so the rows the query does not write keep their content. */
+int wo_dev_trace_spans_host(WoDev* dev, void const* rays, void* spans, void* crossings, size_t n,
+                            uint32_t max_crossings, char* err, size_t errlen);
+/* Point classification (wo_renderer_classify_points_device): n float4 points at
+ * d_points (16-byte aligned) -> n uint32 at d_out, async on `stream`; and the
+ * synchronous host form. */
+int wo_dev_classify_points(WoDev* dev, void const* d_points, void* d_out, size_t n, void* stream, char* err,
+                           size_t errlen);
+int wo_dev_classify_points_host(WoDev* dev, void const* points, void* out, size_t n, char* err, size_t errlen);
 /* Per program record its source node handle (Wo_Renderer::prog_nodes), read by the
  * ray kernels; uploaded with the scene (blocking, after wo_dev_upload_scene). */
 int wo_dev_upload_nodes(WoDev* dev, uint32_t const* nodes, uint32_t n_recs, char* err, size_t errlen);

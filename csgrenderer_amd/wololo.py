@@ -34,6 +34,8 @@ WORK_KINDS = ("segments", "sphere_tests", "halfspace_tests", "bound_tests", "eve
 WO_NODE_INVALID = 0xFFFFFFFF
 # renderer_ext.h WO_RAY_* (Wo_RayHit.flags) and Wo_RayTracer
 RAY_HIT, RAY_EXIT, RAY_ENTERS, RAY_INVALID = 1, 2, 4, 8
+RAY_INSIDE, RAY_TRUNCATED = 16, 32  # Wo_RaySpans.flags
+POINT_INSIDE, POINT_INVALID = 1, 8  # WO_POINT_*
 RAY_TRACER_AUTO, RAY_TRACER_INTERPRETER, RAY_TRACER_LANES = 0, 1, 2
 RAY_TRACERS = {"auto": RAY_TRACER_AUTO, "interpreter": RAY_TRACER_INTERPRETER, "lanes": RAY_TRACER_LANES}
 
@@ -91,7 +93,22 @@ class RayHit(Structure):
 RAY_HIT_FIELDS = [("t", "<f4"), ("flags", "<u4"), ("leaf", "<u4"), ("node", "<u4"), ("normal", "<f4", (3,)),
                   ("material", "<u4")]
 
+
+
+class RayCrossing(Structure):
+    _fields_ = [("t", c_float), ("flags", c_uint32), ("leaf", c_uint32), ("node", c_uint32)]
+
+
+class RaySpans(Structure):
+    _fields_ = [("count", c_uint32), ("flags", c_uint32), ("length", c_float), ("stored", c_uint32)]
+
+
+# numpy views of Wo_RayCrossing / Wo_RaySpans arrays (Renderer.trace_spans returns them)
+RAY_CROSSING_FIELDS = [("t", "<f4"), ("flags", "<u4"), ("leaf", "<u4"), ("node", "<u4")]
+RAY_SPANS_FIELDS = [("count", "<u4"), ("flags", "<u4"), ("length", "<f4"), ("stored", "<u4")]
+
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 32
+assert ctypes.sizeof(RayCrossing) == 16 and ctypes.sizeof(RaySpans) == 16
 assert ctypes.sizeof(Vec3) == 24 and ctypes.sizeof(Quaternion) == 32 and ctypes.sizeof(NodeArgument) == 64
 assert ctypes.sizeof(WoRec) == 32 and ctypes.sizeof(WoMaterial) == 32
 
@@ -167,6 +184,10 @@ SIGNATURES = {
     "wo_renderer_program_nodes": (POINTER(c_uint32), [c_void_p, POINTER(c_uint32)]),
     "wo_renderer_set_ray_tracer": (None, [c_void_p, c_int]),
     "wo_renderer_ray_path": (c_char_p, [c_void_p]),
+    "wo_renderer_trace_spans_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_void_p]),
+    "wo_renderer_trace_spans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_uint32]),
+    "wo_renderer_classify_points_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wo_renderer_classify_points": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
     "wo_renderer_set_jit_async": (None, [c_void_p, c_int]),
     "wo_renderer_jit_pending": (c_int, [c_void_p]),
     "wo_renderer_prepare": (c_int, [c_void_p]),
@@ -438,6 +459,59 @@ class Renderer:
 
     def ray_path(self) -> str:
         return self.lib.wo_renderer_ray_path(self.ptr).decode()
+
+    # ---- ray span queries and point classification (renderer_ext.h wo_renderer_trace_spans ...) ----
+    def trace_spans(self, rays, max_crossings: int, crossings=None):
+        """Every crossing of n rays ((n, 8) float32 Wo_Ray rows) with the solid: returns
+        (spans[n], crossings[max_crossings, n]) as structured arrays (RAY_SPANS_FIELDS,
+        RAY_CROSSING_FIELDS); row k of `crossings` holds every ray's k-th crossing, valid for
+        k < spans["stored"].  `crossings`: a (max_crossings, n) array to fill instead of a new
+        zeroed one (rows that are not written keep its content).  Synchronous."""
+        import numpy as np
+        a = np.ascontiguousarray(rays, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays: an (n, 8) float32 array")
+        n, m = a.shape[0], int(max_crossings)
+        spans = np.zeros(n, dtype=np.dtype(RAY_SPANS_FIELDS))
+        if crossings is None:
+            crossings = np.zeros((m, n), dtype=np.dtype(RAY_CROSSING_FIELDS))
+        elif (crossings.dtype != np.dtype(RAY_CROSSING_FIELDS) or crossings.shape != (m, n)
+              or not crossings.flags.c_contiguous or not crossings.flags.writeable):
+            raise ValueError("crossings: a writable C-contiguous (max_crossings, n) RAY_CROSSING_FIELDS array")
+        if self.lib.wo_renderer_trace_spans(self.ptr, a.ctypes.data_as(c_void_p), spans.ctypes.data_as(c_void_p),
+                                            crossings.ctypes.data_as(c_void_p) if m else None, n, m):
+            raise WololoError(last_error())
+        return spans, crossings
+
+    def trace_spans_device(self, d_rays: int, d_spans: int, d_crossings: int, n: int, max_crossings: int,
+                           stream: int = 0):
+        """n Wo_Ray at device address d_rays -> n Wo_RaySpans at d_spans and the crossing-major
+        Wo_RayCrossing rows at d_crossings (0 with max_crossings = 0), asynchronously on `stream`."""
+        if self.lib.wo_renderer_trace_spans_device(self.ptr, c_void_p(d_rays or None), c_void_p(d_spans or None),
+                                                   c_void_p(d_crossings or None), int(n), int(max_crossings),
+                                                   c_void_p(stream or None)):
+            raise WololoError(last_error())
+
+    def classify_points(self, points):
+        """WO_POINT_INSIDE / 0 / WO_POINT_INVALID per point of an (n, 3) or (n, 4) float32 array
+        (a fourth column is ignored): uint32[n].  Synchronous."""
+        import numpy as np
+        p = np.asarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise ValueError("points: an (n, 3) or (n, 4) float32 array")
+        a = np.zeros((p.shape[0], 4), dtype=np.float32)
+        a[:, :p.shape[1]] = p
+        out = np.zeros(p.shape[0], dtype=np.uint32)
+        if self.lib.wo_renderer_classify_points(self.ptr, a.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p),
+                                                p.shape[0]):
+            raise WololoError(last_error())
+        return out
+
+    def classify_points_device(self, d_points: int, d_out: int, n: int, stream: int = 0):
+        """n float4 points at device address d_points -> n uint32 at d_out, asynchronously on `stream`."""
+        if self.lib.wo_renderer_classify_points_device(self.ptr, c_void_p(d_points or None), c_void_p(d_out or None),
+                                                       int(n), c_void_p(stream or None)):
+            raise WololoError(last_error())
 
     def frame_desc(self, params: RenderParams, tile_rows=16, rank=0, nranks=1) -> WoFrame:
         fr = WoFrame()

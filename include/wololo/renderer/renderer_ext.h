@@ -274,6 +274,66 @@ void wo_renderer_set_ray_tracer(Wo_Renderer* r, Wo_RayTracer tracer);
 /* Which kernel the last ray launch used: "interpreter", "lanes" or "none". */
 char const* wo_renderer_ray_path(Wo_Renderer* r);
 
+/* ---- ray span queries (ray classification) and point classification ----
+ * Every interval of a ray that lies inside the solid, and whether a point does.
+ * The crossings of a ray are the events, in the tracer's key order (t, primitive
+ * ordinal, entry before exit), at which the root's membership changes, with
+ * WO_T_MIN < t <= t_max.  Crossing 0 is what wo_renderer_trace_rays reports for the
+ * ray; the later ones come from the same sweep carried on -- no restart, no new
+ * origin.  Coincident surfaces are decided by the key order alone, one event at a
+ * time, so a zero-length span (two crossings of equal t) is reported, not merged. */
+#define WO_RAY_INSIDE    16u  /* Wo_RaySpans.flags: the root contains the ray's point at WO_T_MIN */
+#define WO_RAY_TRUNCATED 32u  /* Wo_RaySpans.flags: count > max_crossings */
+
+typedef struct Wo_RayCrossing {  /* 16 bytes */
+    float t;                 /* WO_T_MIN < t <= t_max */
+    uint32_t flags;          /* WO_RAY_HIT | WO_RAY_EXIT? | WO_RAY_ENTERS?, as Wo_RayHit.flags */
+    uint32_t leaf;           /* record index in the compiled program */
+    Wo_Node node;            /* the node that leaf was compiled from */
+} Wo_RayCrossing;
+
+typedef struct Wo_RaySpans {     /* 16 bytes per ray */
+    uint32_t count;          /* all crossings in (WO_T_MIN, t_max], however many were stored */
+    uint32_t flags;          /* WO_RAY_INSIDE, WO_RAY_TRUNCATED, WO_RAY_INVALID */
+    float length;            /* total length of the ray inside the solid within (WO_T_MIN, t_max] */
+    uint32_t stored;         /* min(count, max_crossings) */
+} Wo_RaySpans;
+
+/* `length` is summed in fp32, one rounding per operation, in sweep order: len = 0,
+ * t_in = WO_T_MIN; a crossing that enters sets t_in = t; one that leaves adds
+ * (t - t_in); after the last crossing, a ray that is inside with t_max > t_in adds
+ * (t_max - t_in), which is +INFINITY for t_max = +INFINITY.  WO_RAY_INSIDE is also
+ * right for a ray without any event (one inside a lone half-space).  An invalid ray
+ * (as for trace_rays) gets count = stored = 0, length = 0, flags = WO_RAY_INVALID.
+ *
+ * n Wo_Ray at d_rays -> n Wo_RaySpans at d_spans and the crossings at d_crossings,
+ * CROSSING-MAJOR: ray i's k-th crossing is d_crossings[k * n + i], k < stored (a
+ * wave's k-th store is 64 consecutive rows); rows with k >= stored are not written.
+ * count and length cover all crossings whatever max_crossings is, so max_crossings =
+ * 0 (d_crossings may then be NULL) is the thickness query: 16 bytes written per ray.
+ * Device memory, 16-byte aligned, asynchronous on `stream`; everything else as
+ * wo_renderer_trace_rays_device.  Always the interpreter's sweep (ray_path then
+ * says "interpreter"); wo_renderer_set_ray_tracer has no say. */
+int wo_renderer_trace_spans_device(Wo_Renderer* r, Wo_Ray const* d_rays, Wo_RaySpans* d_spans,
+                                   Wo_RayCrossing* d_crossings, size_t n, uint32_t max_crossings, void* stream);
+/* The same from and to host memory (synchronous; includes the copies).  Crossing
+ * rows the query does not write keep the caller's content. */
+int wo_renderer_trace_spans(Wo_Renderer* r, Wo_Ray const* rays, Wo_RaySpans* spans, Wo_RayCrossing* crossings,
+                            size_t n, uint32_t max_crossings);
+
+#define WO_POINT_INSIDE  1u
+#define WO_POINT_INVALID 8u   /* a non-finite coordinate: not classified */
+/* Is each of n points (float4 rows x, y, z, w; w ignored; 16-byte aligned) inside
+ * the solid?  Every leaf is evaluated in fp32, one rounding per operation: a sphere
+ * contains p iff ((g.x g.x + g.y g.y) + g.z g.z) <= r^2 with g = p - c, a half-space
+ * iff ((n.x p.x + n.y p.y) + n.z p.z) <= h; a primitive is the AND of its members,
+ * the operators apply as in wo_scene.h, and an empty scene contains nothing.
+ * d_out[i] = WO_POINT_INSIDE, 0, or WO_POINT_INVALID.  Asynchronous on `stream`,
+ * otherwise as wo_renderer_trace_rays_device. */
+int wo_renderer_classify_points_device(Wo_Renderer* r, float const* d_points, uint32_t* d_out, size_t n, void* stream);
+/* The same from and to host memory (synchronous; includes both copies). */
+int wo_renderer_classify_points(Wo_Renderer* r, float const* points, uint32_t* out, size_t n);
+
 /* Path-tracer kernel selection (results are identical; only speed differs).
  *   AUTO         union-only scenes of more than WOLOLO_LANES_MIN_PRIMS (256)
  *                primitives -> LANES; else scenes of up to WOLOLO_JIT_MAX_PRIMS
@@ -368,7 +428,8 @@ void wo_renderer_clear_error(void);
 /* ---- library-level ---- */
 /* sizeof(type) (field NULL) or offsetof(type, field) as this library was
  * compiled, for the value types of the C ABI (Wo_Vec3, Wo_Quaternion,
- * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame, Wo_Ray, Wo_RayHit);
+ * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame, Wo_Ray, Wo_RayHit,
+ * Wo_RayCrossing, Wo_RaySpans);
  * (size_t)-1 for an unknown name.  Bindings check their mirrors with it. */
 size_t wo_abi_layout(char const* type, char const* field);
 /* Device self-check of the path tracer's fast correctly rounded square root
