@@ -19,6 +19,13 @@ test, not bench.py.
 
     python tools/sky_ray_share.py --out profiles/sky_rays_before.txt
     python tools/sky_ray_share.py --ab 4 --levels 0,1,2
+
+--take-probe counts, for the build --flags names, where the predicate's block runs and how full
+the wave is there (probe builds WO_SKY_RAYS_PROBE 2..9, one count each); --variants times named
+flag sets against each other, e.g. the thresholds of WO_SKY_RAYS_BOUNCE_MIN.
+
+    python tools/sky_ray_share.py --take-probe --flags=-DWO_SKY_RAYS_BOUNCE_MIN=1 --out profiles/sky_rays_take_before.txt
+    python tools/sky_ray_share.py --ab 4 --variants "all=-DWO_SKY_RAYS_BOUNCE_MIN=1;cam=-DWO_SKY_RAYS_BOUNCE_MIN=65"
 """
 import argparse
 import os
@@ -57,6 +64,10 @@ def main():
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--prewarm-s", type=float, default=0.3)
     ap.add_argument("--ab", type=int, default=0, help="alternating rounds timing the levels (0 included as listed)")
+    ap.add_argument("--take-probe", action="store_true",
+                    help="the predicate block's executions and lanes, the bounce and camera iterations (with --flags)")
+    ap.add_argument("--flags", default="", help="--take-probe: the build's WOLOLO_JIT_FLAGS")
+    ap.add_argument("--variants", default=None, help="time named flag sets: 'name=flags;name=flags' (rounds: --ab)")
     ap.add_argument("--cpu", action="store_true", help="the oracle's share too")
     ap.add_argument("--cpu-rays", type=int, default=20000, help="--cpu: camera rays")
     ap.add_argument("--no-gpu", action="store_true")
@@ -105,7 +116,47 @@ def main():
             torch.cuda.synchronize()
             return statistics.median(x.elapsed_time(y) for x, y in ev)
 
-        if a.ab:
+        if a.take_probe:
+            # the loop's structure around the predicate's block, one probe build per count
+            # (wo_device_common.h WO_SKY_RAYS_PROBE 2..9: each adds its count to the segments)
+            r, p = renderer(a.flags)
+            S, k = segments(r, p), r.kernel_info()
+            r.close()
+            say(f"{a.scene} {p.width}x{p.height} {p.spp} spp depth {p.max_depth}, flags '{a.flags}': {S} segments; kernel "
+                f"{k['key'][:16]}, {k['vgprs']} VGPRs, {k['scratch_bytes']} B scratch, {k['lds_bytes']} B LDS")
+            n = {}
+            for kind in range(1, 10):
+                r, p = renderer(f"{a.flags} -DWO_SKY_RAYS_PROBE={kind}")
+                n[kind] = segments(r, p) - S
+                r.close()
+
+            def per(x, y):
+                return f"{x / y:.2f}" if y else "-"
+
+            say(f"predicate: {n[5] + n[4]} rays tested, {n[1]} accepted")
+            say(f"(a) executions of the predicate's block: {n[2]} in camera iterations, {n[3]} in bounce iterations")
+            say(f"(b) lanes under its mask: {n[4]} in camera iterations ({per(n[4], n[2])} a block), {n[5]} in bounce "
+                f"iterations ({per(n[5], n[3])} a block); {per(n[4] + n[5], n[2] + n[3])} a block overall")
+            say(f"(c) bounce iterations that trace: {n[6]}, busy lanes {n[7]} ({per(n[7], n[6])} a trace)")
+            say(f"(d) camera iterations: {n[8]}, jobs {n[9]} ({per(n[9], n[8])} an iteration)")
+        elif a.variants:
+            # named flag sets against each other, as --ab does for the levels
+            vs = [v.split("=", 1) for v in a.variants.split(";") if v]
+            rs = [(name,) + renderer(flags) for name, flags in vs]
+            say(f"{a.scene} {rs[0][2].width}x{rs[0][2].height} {rs[0][2].spp} spp depth {rs[0][2].max_depth}: median of "
+                f"{a.frames} frames a run, {max(a.ab, 1)} alternating rounds")
+            ms = {name: [] for name, _ in vs}
+            for i in range(max(a.ab, 1)):
+                for name, r, p in rs:
+                    ms[name].append(frame_ms(r, p))
+                say(f"round {i + 1}: " + ", ".join(f"{name} {ms[name][-1]:.4f} ms" for name, _ in vs))
+            for (name, flags), (_, r, p) in zip(vs, rs):
+                k = r.kernel_info()
+                say(f"{name} ('{flags}'): median {statistics.median(ms[name]):.4f} ms, spread "
+                    f"{max(ms[name]) - min(ms[name]):.4f}; kernel {k['key'][:16]}, {k['vgprs']} VGPRs, "
+                    f"{k['scratch_bytes']} B scratch, {k['lds_bytes']} B LDS, {segments(r, p)} segments")
+                r.close()
+        elif a.ab:
             rs = [(L,) + renderer(f"-DWO_SKY_RAYS={L}") for L in levels]
             say(f"{a.scene} {rs[0][2].width}x{rs[0][2].height} {rs[0][2].spp} spp depth {rs[0][2].max_depth}: median of "
                 f"{a.frames} frames a run, {a.ab} alternating rounds")
