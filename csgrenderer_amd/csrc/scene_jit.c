@@ -2570,11 +2570,11 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
      * -> 11.35; they replace round 4's ring of camera rays, csg32 3.13 -> 3.07).  Mode
      * 1's ring of ready paths (12 KB per workgroup) does not fit beside an LDS event
      * list at 8 workgroups per CU (csg32_nested 10.55 -> 11.76, csg256 balanced 9.30 ->
-     * 10.59 at 4 waves per SIMD), so the event window is in registers (below); mode 2
-     * rings the camera hits (4 KB). */
+     * 10.59 at 4 waves per SIMD), so the event window is in registers (below).  (Mode 2,
+     * a ring of the camera hits, is gone: pathtrace_block's static_assert refuses it.) */
     bput(&b, "#ifndef WO_CAM_WAVES\n#define WO_CAM_WAVES 1\n#endif\n");
-    /* WO_JIT_LDS_EVENTS=0 (WOLOLO_JIT_FLAGS) puts a small tree's event window in
-     * registers (wodev::Window) instead of the LDS list */
+    /* the event window is in registers (wodev::Window) for every scene;
+     * WO_JIT_LDS_EVENTS=1 (WOLOLO_JIT_FLAGS) brings the LDS list back */
     bput(&b, "#include \"wo_device_common.h\"\n#ifndef WO_JIT_LDS_EVENTS\n#define WO_JIT_LDS_EVENTS 0  // tree depth %u\n#endif\n#define WO_JIT_LDS_PROG %d\n\n",
          tree_depth(prog, n_recs), lds_prog);
     if (use_lut) {
@@ -2864,9 +2864,10 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
                  "      if (!win.empty()) {\n"
                  "        if (r != root) { wodev::hit_from_key(key, r, hit); return true; }\n"
                  "        root = r;\n"
-                 "        win.next(key);\n"
-                 "        WO_WK(WO_WORK_SWEEP_STEPS);\n"
-                 "        {\n"
+                 "        // (the LDS list is not empty while it holds a dropped key, and has no next event\n"
+                 "        // once that key is delivered: nothing to toggle then, the top of the loop re-collects)\n"
+                 "        if (win.next(key)) {\n"
+                 "          WO_WK(WO_WORK_SWEEP_STEPS);\n"
                  "          uint32_t ord = ((uint32_t)key) >> 12;\n"
                  "          uint32_t w = ord >> 5, m = 1u << (ord & 31u);\n");
             bput(&b, "#if WO_HBITS_LDS\n          bits[w] ^= m;\n#else\n");
@@ -3025,9 +3026,10 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
             bput(&b,
                  "        if (r != root) { wodev::hit_from_key(key, r, hit); return true; }\n"
                  "        root = r;\n"
-                 "        win.next(key);\n"
-                 "        WO_WK(WO_WORK_SWEEP_STEPS);\n"
-                 "        {\n"
+                 "        // (the LDS list is not empty while it holds a dropped key, and has no next event\n"
+                 "        // once that key is delivered: nothing to toggle then, the top of the loop re-collects)\n"
+                 "        if (win.next(key)) {\n"
+                 "          WO_WK(WO_WORK_SWEEP_STEPS);\n"
                  "          uint32_t ord = ((uint32_t)key) >> 12;\n"
                  "          uint32_t w = ord >> 5, m = 1u << (ord & 31u);\n");
             for (uint32_t w = 0; w < nw; ++w) bput(&b, "          bits[%u] ^= w == %uu ? m : 0u;\n", w, w);
