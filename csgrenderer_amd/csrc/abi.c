@@ -43,6 +43,16 @@ static const AbiField kAbi[] = {
     T(Wo_RayCrossing), F(Wo_RayCrossing, t), F(Wo_RayCrossing, flags), F(Wo_RayCrossing, leaf),
     F(Wo_RayCrossing, node),
     T(Wo_RaySpans), F(Wo_RaySpans, count), F(Wo_RaySpans, flags), F(Wo_RaySpans, length), F(Wo_RaySpans, stored),
+    T(Wo_MassGrid), F(Wo_MassGrid, lo), F(Wo_MassGrid, hi), F(Wo_MassGrid, axis), F(Wo_MassGrid, nu), F(Wo_MassGrid, nv),
+    F(Wo_MassGrid, v_begin), F(Wo_MassGrid, v_count), F(Wo_MassGrid, reserved),
+    T(Wo_MassPlan), F(Wo_MassPlan, o_axis), F(Wo_MassPlan, pad), F(Wo_MassPlan, t_max), F(Wo_MassPlan, scale),
+    F(Wo_MassPlan, k), F(Wo_MassPlan, q0), F(Wo_MassPlan, q1), F(Wo_MassPlan, u0), F(Wo_MassPlan, hu),
+    F(Wo_MassPlan, v0), F(Wo_MassPlan, hv),
+    T(Wo_MassSums), F(Wo_MassSums, lo), F(Wo_MassSums, hi), F(Wo_MassSums, rays), F(Wo_MassSums, rays_hit),
+    F(Wo_MassSums, crossings), F(Wo_MassSums, reserved),
+    T(Wo_MassProperties), F(Wo_MassProperties, volume), F(Wo_MassProperties, centroid), F(Wo_MassProperties, inertia),
+    F(Wo_MassProperties, projected_area), F(Wo_MassProperties, cell), F(Wo_MassProperties, rays),
+    F(Wo_MassProperties, crossings),
 };
 
 #undef T

@@ -883,6 +883,64 @@ int wo_renderer_classify_points(Wo_Renderer* r, float const* points, uint32_t* o
     return 0;
 }
 
+/* mass properties: the grid is checked and planned on the host (mass.c), and the kernel gets
+ * the plan's own numbers, so host and device quantise alike */
+static int mass_launch_of(Wo_MassGrid const* grid, WoMassLaunch* ml) {
+    Wo_MassPlan p;
+    if (wo_mass_grid_plan(grid, &p)) return -1;
+    ml->o_axis = p.o_axis;
+    ml->t_max = p.t_max;
+    ml->scale = p.scale;
+    ml->u0 = p.u0;
+    ml->hu = p.hu;
+    ml->v0 = p.v0;
+    ml->hv = p.hv;
+    ml->q0 = p.q0;
+    ml->q1 = p.q1;
+    ml->axis = grid->axis;
+    ml->nu = grid->nu;
+    ml->v_begin = grid->v_begin;
+    ml->v_count = grid->v_count;
+    return 0;
+}
+
+int wo_renderer_mass_sums_device(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_MassSums* d_sums, void* stream) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    WoMassLaunch ml;
+    if (mass_launch_of(grid, &ml)) return -1;
+    if (!d_sums) {
+        wo_set_error("mass_sums: NULL sums buffer");
+        return -1;
+    }
+    char err[256] = {0};
+    if (wo_dev_mass_sums(r->dev, &ml, d_sums, stream, err, sizeof err)) {
+        wo_set_error("mass launch failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_mass_properties(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_MassProperties* out,
+                                Wo_MassSums* sums_or_null) {
+    if (!r) return -1;
+    if (sync_device(r)) return -1;
+    WoMassLaunch ml;
+    if (mass_launch_of(grid, &ml)) return -1;
+    if (!out) {
+        wo_set_error("mass_properties: NULL result");
+        return -1;
+    }
+    Wo_MassSums sums;
+    char err[256] = {0};
+    if (wo_dev_mass_sums_host(r->dev, &ml, &sums, err, sizeof err)) {
+        wo_set_error("mass query failed: %s", err);
+        return -1;
+    }
+    if (sums_or_null) *sums_or_null = sums;
+    return wo_mass_properties_from_sums(grid, &sums, out);
+}
+
 /* oracle.c normalize3 / sqrt_pt, one rounding per operation (-ffp-contract=off) */
 static void normalize3f(float v[3]) {
     const float dot = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];

@@ -1541,6 +1541,180 @@ __global__ __launch_bounds__(kBlock) void trace_spans_kernel(const WoRec* __rest
     }
 }
 
+// ---------------------------------------------------------------------------
+// Mass properties (wo_renderer_mass_sums_device): a grid of parallel rays made in
+// registers from the plan (renderer_ext.h Wo_MassPlan), each span quantised and
+// integrated as trace_spans sweeps it, the ten sums and three counters of
+// Wo_MassSums accumulated as exact integers.  No ray is read and no row written:
+// a workgroup's only traffic to global memory, the program apart, is up to 23 64-bit
+// atomic adds at its end.
+// ---------------------------------------------------------------------------
+constexpr int kMassSlots = 23;  // Wo_MassSums: lo[10], hi[10], rays, rays_hit, crossings (reserved is not touched)
+static_assert(0x1p-9f > WO_T_MIN, "Wo_MassPlan.pad: a surface on the near face must be a crossing");
+
+// Where the accumulators live between a lane's rays (measured; the sums
+// are the same integers whichever is used):
+//   kMassRegs   per lane in registers over the whole loop, reduced once at the end;
+//   kMassShfl   reduced across the wave after every ray, kept wave-uniform;
+//   kMassLds    every lane adds into its wave's slots in LDS (64-bit ds_add).
+enum { kMassRegs = 0, kMassShfl = 1, kMassLds = 2 };
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
+    return v;
+}
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+    return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
+}
+
+// kTile: a wave takes an 8 x 8 tile of cells (lane = 8 row + column), else a 64 x 1
+// strip of one row.  Items (tiles or strips) are numbered row-major over the row
+// range and dealt to the waves by the grid-stride loop; lane 0 of an item is always
+// a cell of the grid.
+template <bool kProgInLds, int kN, bool kTile, int kRed>
+__global__ __launch_bounds__(kBlock) void mass_grid_kernel(const WoRec* __restrict__ gprog, uint32_t nrec, KLayout lay,
+                                                           WoMassLaunch ml, unsigned long long* __restrict__ sums,
+                                                           uint32_t block_flush) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uni(tid >> 6);
+
+    uint32_t* scratch = smem;
+    InterpTracer<false> tr;
+    if constexpr (kProgInLds) {
+        const uint4* src = reinterpret_cast<const uint4*>(gprog);
+        uint4* dst = reinterpret_cast<uint4*>(smem);
+        for (uint32_t i = tid; i < nrec * 2u; i += kBlock) dst[i] = src[i];
+        __syncthreads();
+        tr.prog.p = reinterpret_cast<const WoRec*>(smem);
+        scratch = smem + nrec * 8u;
+    } else {
+        tr.prog.p = gprog;
+    }
+    uint32_t* ws = scratch + wave * lay.wave_words;
+    tr.nrec = nrec;
+    tr.codes = ws;
+    tr.ordpc = ws + lay.ordpc_off;
+    tr.hib = ws + lay.hib_off;
+    tr.lane = lane;
+
+    uint64_t acc[kMassSlots];
+#pragma unroll
+    for (int s = 0; s < kMassSlots; ++s) acc[s] = 0ull;
+    // (a static array beside the dynamic one; only the kMassLds instantiations have it)
+    unsigned long long* slots = nullptr;
+    if constexpr (kRed == kMassLds) {
+        __shared__ unsigned long long mass_slots[kBlock / 64u][kMassSlots + 1];
+        slots = mass_slots[wave];
+        if (lane < (uint32_t)kMassSlots) slots[lane] = 0ull;  // the wave's own slots: no barrier needed
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+
+    const uint32_t across = kTile ? (ml.nu + 7u) >> 3 : (ml.nu + 63u) >> 6;
+    const uint32_t down = kTile ? (ml.v_count + 7u) >> 3 : ml.v_count;
+    const uint64_t items = (uint64_t)across * down;
+    const uint32_t li = kTile ? (lane & 7u) : lane, lj = kTile ? (lane >> 3) : 0u;
+    const uint64_t stride = (uint64_t)gridDim.x * (kBlock / 64u);
+    for (uint64_t item = (uint64_t)blockIdx.x * (kBlock / 64u) + wave; item < items; item += stride) {
+        const uint32_t iy = (uint32_t)(item / across), ix = (uint32_t)(item - (uint64_t)iy * across);
+        const uint32_t ci = ix * (kTile ? 8u : 64u) + li, cj = iy * (kTile ? 8u : 1u) + lj;
+        const bool in = ci < ml.nu && cj < ml.v_count;
+        // lanes past the grid's edge sweep lane 0's ray (always a cell) and drop the result
+        const uint32_t i = in ? ci : uni(ci), j = ml.v_begin + (in ? cj : uni(cj));
+        const uint32_t i2 = 2u * i + 1u, j2 = 2u * j + 1u;
+        // two roundings each: the product, then the sum (no contraction in this file)
+        const float pu = (float)i2 * ml.hu, pv = (float)j2 * ml.hv;
+        const float cu = ml.u0 + pu, cv = ml.v0 + pv;
+        F3 o, d;
+        if (ml.axis == 0u) {
+            o = f3(ml.o_axis, cu, cv);
+            d = f3(1.0f, 0.0f, 0.0f);
+        } else if (ml.axis == 1u) {
+            o = f3(cv, ml.o_axis, cu);
+            d = f3(0.0f, 1.0f, 0.0f);
+        } else {
+            o = f3(cu, cv, ml.o_axis);
+            d = f3(0.0f, 0.0f, 1.0f);
+        }
+        uint32_t qa = ml.q0, m0 = 0u;
+        uint64_t m1 = 0ull, m2 = 0ull;
+        auto close = [&](uint32_t qb) {  // the span [qa, qb]: qa <= qb <= 2^20, so a^3 <= 2^60
+            const uint64_t a = qa, b = qb;
+            m0 += qb - qa;
+            m1 += b * b - a * a;
+            m2 += b * b * b - a * a * a;
+        };
+        const SpanSum s = trace_spans<kN>(tr, o, d, ml.t_max, [&](uint64_t key, uint32_t root_after, uint32_t) {
+            const float t = __uint_as_float((uint32_t)(key >> 32));
+            const uint32_t q = (uint32_t)rintf(t * ml.scale);  // exact product, half to even
+            const uint32_t c = min(max(q, ml.q0), ml.q1);
+            if (root_after)
+                qa = c;
+            else
+                close(c);
+        });
+        if (s.root) close(ml.q1);
+        // a ray's ten terms, each below 2^63, split into 32-bit limbs (Wo_MassSums): with at
+        // most 2^31 rays added into one buffer a limb sum stays below 2^31 * 2^32 = 2^63
+        auto accumulate = [&](int k, uint64_t v) {
+            if constexpr (kRed == kMassRegs)
+                acc[k] += v;
+            else if constexpr (kRed == kMassShfl)
+                acc[k] += uni64(wave_sum(v));
+            else if (v != 0ull)
+                (void)atomicAdd(&slots[k], (unsigned long long)v);
+        };
+        // (m0 = 0 leaves m1 = m2 = 0: a wave none of whose rays met the solid adds counters only)
+        if (__ballot(in && m0 != 0u) != 0ull) {
+            const uint64_t w0 = in ? m0 : 0u, w1 = in ? m1 : 0ull, w2 = in ? m2 : 0ull;
+            const uint64_t term[10] = {w0,           w0 * i2, w0 * j2,      w1,      w0 * i2 * i2,
+                                       w0 * j2 * j2, w2,      w0 * i2 * j2, w1 * i2, w1 * j2};
+#pragma unroll
+            for (int k = 0; k < 10; ++k) {
+                accumulate(k, term[k] & 0xFFFFFFFFull);
+                accumulate(10 + k, term[k] >> 32);
+            }
+        }
+        accumulate(20, in ? 1ull : 0ull);
+        accumulate(21, in && m0 > 0u ? 1ull : 0ull);
+        accumulate(22, in ? (uint64_t)s.count : 0ull);
+    }
+    if constexpr (kRed == kMassLds) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    uint64_t total[kMassSlots];  // the wave's, wave-uniform
+#pragma unroll
+    for (int k = 0; k < kMassSlots; ++k) {
+        if constexpr (kRed == kMassRegs)
+            total[k] = wave_sum(acc[k]);
+        else if constexpr (kRed == kMassShfl)
+            total[k] = acc[k];
+        else
+            total[k] = __hip_atomic_load(&slots[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);  // the wave's own adds
+    }
+    if (!block_flush) {  // one atomic add per slot and wave
+#pragma unroll
+        for (int k = 0; k < kMassSlots; ++k)
+            if (lane == 0u && total[k] != 0ull) (void)atomicAdd(&sums[k], (unsigned long long)total[k]);
+        return;
+    }
+    // One atomic add per slot and WORKGROUP: all of a launch's adds go to the same two
+    // cache lines, where they are served one after another, so their number is what the
+    // tail of the kernel costs.  The waves' totals meet in the dynamic LDS,
+    // which the program and the scratch no longer need (the host sizes it for this too).
+    __syncthreads();
+    unsigned long long* red = reinterpret_cast<unsigned long long*>(smem);  // [waves][kMassSlots]
+    if (lane == 0u) {
+#pragma unroll
+        for (int k = 0; k < kMassSlots; ++k) red[wave * kMassSlots + k] = total[k];
+    }
+    __syncthreads();
+    if (tid < (uint32_t)kMassSlots) {
+        unsigned long long v = 0ull;
+        for (uint32_t w = 0; w < kBlock / 64u; ++w) v += red[w * kMassSlots + tid];
+        if (v != 0ull) (void)atomicAdd(&sums[tid], v);
+    }
+}
+constexpr size_t kMassReduceLds = (kBlock / 64u) * kMassSlots * sizeof(unsigned long long);
+
 // Point membership classification (wo_renderer_classify_points_device): one point
 // (a float4, w ignored) per lane, the program walked once by the wave, the root
 // evaluated on pass 1's bit stack.  Each leaf in fp32, one rounding per operation:
@@ -2337,6 +2511,23 @@ static const void* span_kernel_of(int window) {
 static const void* span_kernel(PathKind kind, int window) {
     return kind == kInterpLds ? span_kernel_of<true>(window) : span_kernel_of<false>(window);
 }
+// a mass launch's kernel: the program in LDS or not, the window, the wave's footprint, the accumulators' home
+template <bool kProgInLds, int kN, bool kTile>
+static const void* mass_kernel_red(int red) {
+    switch (red) {
+    case kMassShfl: return (const void*)mass_grid_kernel<kProgInLds, kN, kTile, kMassShfl>;
+    case kMassLds: return (const void*)mass_grid_kernel<kProgInLds, kN, kTile, kMassLds>;
+    default: return (const void*)mass_grid_kernel<kProgInLds, kN, kTile, kMassRegs>;
+    }
+}
+template <bool kProgInLds>
+static const void* mass_kernel_of(int window, bool tile, int red) {
+    if (window == 8) return tile ? mass_kernel_red<kProgInLds, 8, true>(red) : mass_kernel_red<kProgInLds, 8, false>(red);
+    return tile ? mass_kernel_red<kProgInLds, 16, true>(red) : mass_kernel_red<kProgInLds, 16, false>(red);
+}
+static const void* mass_kernel(PathKind kind, int window, bool tile, int red) {
+    return kind == kInterpLds ? mass_kernel_of<true>(window, tile, red) : mass_kernel_of<false>(window, tile, red);
+}
 static bool is_lane_kind(PathKind kind) { return kind < kJit; }
 
 // The path kernel of the last launch: key_hex (65 bytes) gets the specialised
@@ -2748,6 +2939,107 @@ extern "C" int wo_dev_trace_spans_host(WoDev* dev, void const* rays, void* spans
     if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
     if (e != hipSuccess) {
         set_err(err, errlen, "span query", e);
+        return -1;
+    }
+    return 0;
+}
+
+// ---- mass properties ----
+
+// The mass kernel's form (DESIGN 3.11 holds the measurements; the sums do not depend
+// on it): WOLOLO_MASS_TILE = 8x8 | 64x1, WOLOLO_MASS_WINDOW = 8 | 16,
+// WOLOLO_MASS_REDUCE = regs | shfl | lds (measurement).
+static bool mass_tile() {
+    const char* v = getenv("WOLOLO_MASS_TILE");
+    return !(v && strcmp(v, "64x1") == 0);
+}
+static int mass_window() {
+    const char* v = getenv("WOLOLO_MASS_WINDOW");
+    return v && atoi(v) == 8 ? 8 : 16;
+}
+static int mass_reduce() {
+    const char* v = getenv("WOLOLO_MASS_REDUCE");
+    if (v && strcmp(v, "shfl") == 0) return kMassShfl;
+    if (v && strcmp(v, "lds") == 0) return kMassLds;
+    return kMassRegs;
+}
+// WOLOLO_MASS_FLUSH = wave (measurement): every wave adds its totals to the sums itself
+static uint32_t mass_block_flush() {
+    const char* v = getenv("WOLOLO_MASS_FLUSH");
+    return v && strcmp(v, "wave") == 0 ? 0u : 1u;
+}
+
+extern "C" int wo_dev_mass_sums(WoDev* dev, WoMassLaunch const* ml, void* d_sums, void* stream_v, char* err,
+                                size_t errlen) {
+    hipStream_t stream = (hipStream_t)stream_v;  // NULL = the null stream (HIP convention)
+    if (!dev->d_prog || !dev->d_nodes || dev->n_nodes != dev->n_recs) {
+        snprintf(err, errlen, "no scene (or no node table) on the device");
+        return -1;
+    }
+    if (!d_sums || ((uintptr_t)d_sums & 7u)) {
+        snprintf(err, errlen, "the sums' buffer must be device memory, 8-byte aligned");
+        return -1;
+    }
+    if (ml->axis > 2u || ml->nu == 0u || ml->nu > 32768u || ml->v_count == 0u || ml->v_count > 32768u ||
+        ml->v_begin > 32768u - ml->v_count) {
+        snprintf(err, errlen, "bad mass grid");
+        return -1;
+    }
+    if (dev->n_prims >= (1u << 20)) {
+        snprintf(err, errlen, "scene has %u primitives (max %u)", dev->n_prims, (1u << 20) - 1u);
+        return -1;
+    }
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    PathKind kind;
+    size_t dyn_lds = 0;
+    KLayout lay = {};
+    if (interp_plan(dev->n_recs, dev->n_prims, &lay, &kind, &dyn_lds, err, errlen)) return -1;
+    if (dyn_lds < kMassReduceLds) dyn_lds = kMassReduceLds;  // the workgroup's reduction reuses the dynamic LDS
+    const bool tile = mass_tile();
+    const void* kernel = mass_kernel(kind, mass_window(), tile, mass_reduce());
+    uint32_t block_flush = mass_block_flush();
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, dyn_lds);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    // one item (tile or strip) per wave: ray_grid's count for as many lanes
+    const uint64_t items = tile ? (uint64_t)((ml->nu + 7u) / 8u) * ((ml->v_count + 7u) / 8u)
+                                : (uint64_t)((ml->nu + 63u) / 64u) * ml->v_count;
+    WoMassLaunch launch = *ml;
+    unsigned long long* sums = (unsigned long long*)d_sums;
+    void* args[] = {&dev->d_prog, &dev->n_recs, &lay, &launch, &sums, &block_flush};
+    (void)hipLaunchKernel(kernel, dim3(ray_grid(dev, (size_t)(items * 64u), per_cu)), dim3(kBlock), args, dyn_lds, stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err(err, errlen, "mass kernel launch", e);
+        return -1;
+    }
+    dev->ray_kind = (uint32_t)kind;
+    dev->ray_last = true;
+    return 0;
+}
+
+extern "C" int wo_dev_mass_sums_host(WoDev* dev, WoMassLaunch const* ml, void* sums, char* err, size_t errlen) {
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    const size_t bytes = 24u * sizeof(unsigned long long);  // Wo_MassSums
+    if (ensure_buffer(&dev->d_rayio, &dev->rayio_cap, bytes, err, errlen)) return -1;
+    e = hipMemsetAsync(dev->d_rayio, 0, bytes, dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipMemset(sums)", e);
+        return -1;
+    }
+    if (wo_dev_mass_sums(dev, ml, dev->d_rayio, dev->stream, err, errlen)) return -1;
+    e = hipMemcpyAsync(sums, dev->d_rayio, bytes, hipMemcpyDeviceToHost, dev->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "mass query", e);
         return -1;
     }
     return 0;

@@ -100,6 +100,19 @@ int wo_dev_trace_spans_host(WoDev* dev, void const* rays, void* spans, void* cro
 int wo_dev_classify_points(WoDev* dev, void const* d_points, void* d_out, size_t n, void* stream, char* err,
                            size_t errlen);
 int wo_dev_classify_points_host(WoDev* dev, void const* points, void* out, size_t n, char* err, size_t errlen);
+/* Mass properties (renderer_ext.h wo_renderer_mass_sums_device): what the kernel needs
+ * of a checked Wo_MassGrid and its Wo_MassPlan.  The kernel ADDS the row range's
+ * sums into the Wo_MassSums at d_sums (device memory, 8-byte aligned), async on
+ * `stream`; the host form zeroes a device buffer, runs and copies the 192 bytes
+ * back (synchronous).  Always the interpreter's sweep. */
+typedef struct WoMassLaunch {
+    float o_axis, t_max, scale;
+    float u0, hu, v0, hv;
+    uint32_t q0, q1;
+    uint32_t axis, nu, v_begin, v_count;
+} WoMassLaunch;
+int wo_dev_mass_sums(WoDev* dev, WoMassLaunch const* ml, void* d_sums, void* stream, char* err, size_t errlen);
+int wo_dev_mass_sums_host(WoDev* dev, WoMassLaunch const* ml, void* sums, char* err, size_t errlen);
 /* Per program record its source node handle (Wo_Renderer::prog_nodes), read by the
  * ray kernels; uploaded with the scene (blocking, after wo_dev_upload_scene). */
 int wo_dev_upload_nodes(WoDev* dev, uint32_t const* nodes, uint32_t n_recs, char* err, size_t errlen);

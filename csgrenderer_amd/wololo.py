@@ -107,6 +107,38 @@ class RaySpans(Structure):
 RAY_CROSSING_FIELDS = [("t", "<f4"), ("flags", "<u4"), ("leaf", "<u4"), ("node", "<u4")]
 RAY_SPANS_FIELDS = [("count", "<u4"), ("flags", "<u4"), ("length", "<f4"), ("stored", "<u4")]
 
+
+# renderer_ext.h Wo_MassGrid / Wo_MassPlan / Wo_MassSums / Wo_MassProperties (mass properties by ray-grid integration)
+class MassGrid(Structure):
+    _fields_ = [("lo", c_float * 3), ("hi", c_float * 3), ("axis", c_uint32), ("nu", c_uint32), ("nv", c_uint32),
+                ("v_begin", c_uint32), ("v_count", c_uint32), ("reserved", c_uint32)]
+
+
+class MassPlan(Structure):
+    _fields_ = [("o_axis", c_float), ("pad", c_float), ("t_max", c_float), ("scale", c_float), ("k", ctypes.c_int32),
+                ("q0", c_uint32), ("q1", c_uint32), ("u0", c_float), ("hu", c_float), ("v0", c_float), ("hv", c_float)]
+
+
+class MassSums(Structure):
+    _fields_ = [("lo", ctypes.c_uint64 * 10), ("hi", ctypes.c_uint64 * 10), ("rays", ctypes.c_uint64),
+                ("rays_hit", ctypes.c_uint64), ("crossings", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+    def as_dict(self):
+        """{"sums": the ten sums as Python integers (lo + hi * 2^32), "lo", "hi", "rays", "rays_hit", "crossings"}."""
+        lo, hi = [int(x) for x in self.lo], [int(x) for x in self.hi]
+        return {"sums": [a + (b << 32) for a, b in zip(lo, hi)], "lo": lo, "hi": hi, "rays": int(self.rays),
+                "rays_hit": int(self.rays_hit), "crossings": int(self.crossings)}
+
+
+class MassProperties(Structure):
+    _fields_ = [("volume", c_double), ("centroid", c_double * 3), ("inertia", c_double * 9),
+                ("projected_area", c_double), ("cell", c_double * 3), ("rays", ctypes.c_uint64),
+                ("crossings", ctypes.c_uint64)]
+
+
+MASS_MAX_CELLS = 32768
+assert ctypes.sizeof(MassGrid) == 48 and ctypes.sizeof(MassSums) == 192
+
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 32
 assert ctypes.sizeof(RayCrossing) == 16 and ctypes.sizeof(RaySpans) == 16
 assert ctypes.sizeof(Vec3) == 24 and ctypes.sizeof(Quaternion) == 32 and ctypes.sizeof(NodeArgument) == 64
@@ -188,6 +220,10 @@ SIGNATURES = {
     "wo_renderer_trace_spans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_uint32]),
     "wo_renderer_classify_points_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wo_renderer_classify_points": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+    "wo_mass_grid_plan": (c_int, [POINTER(MassGrid), POINTER(MassPlan)]),
+    "wo_mass_properties_from_sums": (c_int, [POINTER(MassGrid), POINTER(MassSums), POINTER(MassProperties)]),
+    "wo_renderer_mass_sums_device": (c_int, [c_void_p, POINTER(MassGrid), c_void_p, c_void_p]),
+    "wo_renderer_mass_properties": (c_int, [c_void_p, POINTER(MassGrid), POINTER(MassProperties), POINTER(MassSums)]),
     "wo_renderer_set_jit_async": (None, [c_void_p, c_int]),
     "wo_renderer_jit_pending": (c_int, [c_void_p]),
     "wo_renderer_prepare": (c_int, [c_void_p]),
@@ -513,6 +549,21 @@ class Renderer:
                                                        int(n), c_void_p(stream or None)):
             raise WololoError(last_error())
 
+    # ---- mass properties (renderer_ext.h wo_renderer_mass_sums_device ...) ----
+    def mass_sums_device(self, grid: MassGrid, d_sums: int, stream: int = 0):
+        """Adds the exact sums of the grid's row range into the Wo_MassSums (192 bytes, zeroed by
+        the caller) at device address d_sums, asynchronously on `stream`."""
+        if self.lib.wo_renderer_mass_sums_device(self.ptr, ctypes.byref(grid), c_void_p(d_sums or None),
+                                                 c_void_p(stream or None)):
+            raise WololoError(last_error())
+
+    def mass_properties(self, grid: MassGrid):
+        """(MassProperties, MassSums) of the solid inside the grid's clip box.  Synchronous."""
+        props, sums = MassProperties(), MassSums()
+        if self.lib.wo_renderer_mass_properties(self.ptr, ctypes.byref(grid), ctypes.byref(props), ctypes.byref(sums)):
+            raise WololoError(last_error())
+        return props, sums
+
     def frame_desc(self, params: RenderParams, tile_rows=16, rank=0, nranks=1) -> WoFrame:
         fr = WoFrame()
         if self.lib.wo_renderer_frame_desc(self.ptr, ctypes.byref(params), tile_rows, rank, nranks,
@@ -681,6 +732,32 @@ def abi_layout(type_name: str, field: str | None = None) -> int:
     """sizeof / offsetof as the C library was compiled (wo_abi_layout); -1 if unknown."""
     v = load().wo_abi_layout(type_name.encode(), field.encode() if field else None)
     return -1 if v == ctypes.c_size_t(-1).value else int(v)
+
+
+def mass_grid(lo, hi, axis: int, nu: int, nv: int, v_begin: int = 0, v_count: int | None = None) -> MassGrid:
+    """A Wo_MassGrid over the clip box [lo, hi]; the whole grid unless a row range is given."""
+    g = MassGrid()
+    g.lo[:] = [float(x) for x in lo]
+    g.hi[:] = [float(x) for x in hi]
+    g.axis, g.nu, g.nv, g.v_begin = int(axis), int(nu), int(nv), int(v_begin)
+    g.v_count = int(nv - v_begin if v_count is None else v_count)
+    return g
+
+
+def mass_grid_plan(grid: MassGrid) -> MassPlan:
+    """wo_mass_grid_plan (host only): what host and kernel derive from a grid."""
+    plan = MassPlan()
+    if load().wo_mass_grid_plan(ctypes.byref(grid), ctypes.byref(plan)):
+        raise WololoError(last_error())
+    return plan
+
+
+def mass_properties_from_sums(grid: MassGrid, sums: MassSums) -> MassProperties:
+    """wo_mass_properties_from_sums (host only): the properties of a whole grid's sums."""
+    props = MassProperties()
+    if load().wo_mass_properties_from_sums(ctypes.byref(grid), ctypes.byref(sums), ctypes.byref(props)):
+        raise WololoError(last_error())
+    return props
 
 
 JIT_ORIGINS = ("process", "disk", "compiled")

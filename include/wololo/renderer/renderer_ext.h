@@ -334,6 +334,92 @@ int wo_renderer_classify_points_device(Wo_Renderer* r, float const* d_points, ui
 /* The same from and to host memory (synchronous; includes both copies). */
 int wo_renderer_classify_points(Wo_Renderer* r, float const* points, uint32_t* out, size_t n);
 
+/* ---- mass properties (volume, centre of mass, inertia) by ray-grid integration ----
+ * A grid of nu x nv parallel rays along +axis through a clip box; every span of a ray
+ * inside the solid is integrated as it is swept.  The device accumulates EXACT
+ * integers, so the sums do not depend on launch geometry, wave order or how many
+ * calls or devices share a grid, and a CPU reference can match them bit for bit. */
+typedef struct Wo_MassGrid {        /* 48 bytes */
+    float lo[3], hi[3];             /* clip box: finite, lo < hi on every axis */
+    uint32_t axis;                  /* 0, 1, 2: rays run along +axis; u = (axis+1)%3, v = (axis+2)%3 */
+    uint32_t nu, nv;                /* cells (= rays) across u and v, 1 .. 32768 each */
+    uint32_t v_begin, v_count;      /* rows j in [v_begin, v_begin + v_count) of the nv rows; v_count >= 1 */
+    uint32_t reserved;              /* 0 */
+} Wo_MassGrid;
+#define WO_MASS_MAX_CELLS 32768u
+
+typedef struct Wo_MassPlan {        /* what host and kernel derive from a grid; all fp32 ops single-rounded */
+    float o_axis, pad, t_max, scale;/* ray origin on the axis, 0x1p-9f, pad + (hi-lo)[axis], 2^k */
+    int32_t k;
+    uint32_t q0, q1;                /* Q(pad), Q(t_max) */
+    float u0, hu, v0, hv;           /* lo[u], (hi[u]-lo[u]) / (float)(2*nu); same for v */
+} Wo_MassPlan;
+
+typedef struct Wo_MassSums {        /* 192 bytes, exact */
+    uint64_t lo[10], hi[10];        /* sum s = lo[s] + hi[s] * 2^32 */
+    uint64_t rays, rays_hit, crossings, reserved;
+} Wo_MassSums;
+
+typedef struct Wo_MassProperties {
+    double volume, centroid[3], inertia[9];  /* unit density, about the centroid, row-major, off-diagonals -int(ab) */
+    double projected_area;                   /* rays_hit * cell area */
+    double cell[3];                          /* 2hu, 2hv, 2^-k */
+    uint64_t rays, crossings;
+} Wo_MassProperties;
+
+/* The plan.  pad = 0x1p-9f (above WO_T_MIN, so a surface on the box's near face is a
+ * crossing); o_axis = lo[axis] - pad; t_max = pad + (hi[axis] - lo[axis]), the
+ * difference and the sum one fp32 operation each.  frexpf(t_max) = (m, e): k = 20 - e,
+ * scale = 2^k; |k| > 100 is rejected.  Q(t) = (uint32) rintf(t * scale), half to even;
+ * scale is a power of two, so the product is exact and Q(t) <= 2^20 for t <= t_max.
+ * u0 = lo[u], hu = (hi[u] - lo[u]) / (float)(2 nu) (two operations); v likewise.
+ * -1 with wo_renderer_last_error for a bad grid: a non-finite value (t_max included),
+ * lo >= hi, axis > 2, a count of 0 or above 32768, v_count = 0, a row range that
+ * leaves nv, or reserved != 0.  Host arithmetic, no device needed.
+ *
+ * Ray (i, j), 0 <= i < nu, j a row of the range: origin o_axis on the axis,
+ * u0 + (float)(2i+1) * hu on u and v0 + (float)(2j+1) * hv on v (a product and a sum,
+ * not contracted), direction +e_axis, t_max the plan's.  Its crossings are exactly
+ * those wo_renderer_trace_spans reports for that Wo_Ray.
+ *
+ * Per ray, with c(t) = min(max(Q(t), q0), q1): qa = q0 if the ray carries
+ * WO_RAY_INSIDE; a crossing that enters sets qa = c(t); one that leaves at
+ * qb = c(t) adds m0 += qb - qa, m1 += qb^2 - qa^2, m2 += qb^3 - qa^3; a ray still
+ * inside after its last crossing closes at qb = q1 (an unbounded half-space, a solid
+ * cut by the far face).  The box is therefore a true clip box: the part of a span
+ * nearer than pad clamps to q0, the part beyond t_max is never swept.
+ *
+ * With i' = 2i+1 and j' = 2j+1 (j counted in the whole grid), the ten sums over the
+ * rays are, in order: m0, m0 i', m0 j', m1, m0 i'^2, m0 j'^2, m2, m0 i' j', m1 i',
+ * m1 j'.  Every ray's term x is below 2^63 (m2 <= 2^60) and adds x & 0xFFFFFFFF to
+ * lo[s] and x >> 32 to hi[s]: up to 2^31 rays accumulated into one Wo_MassSums
+ * cannot overflow a limb.  rays counts every ray of the row range, rays_hit those
+ * with m0 > 0, crossings sums the rays' Wo_RaySpans.count; reserved is not touched. */
+int wo_mass_grid_plan(Wo_MassGrid const* grid, Wo_MassPlan* plan);
+/* The properties of the column model, in double, from (partial sums added up to) a
+ * whole grid: each ray stands for a column of 2hu x 2hv.  h = 2^-k, A = (2hu)(2hv),
+ * S0..S9 the ten sums (lo + hi 2^32, exact in unsigned __int128):
+ *   volume V = A h S0;  local means  u = hu S1/S0,  v = hv S2/S0,  t = (h/2) S3/S0;
+ *   centroid (lo[u] + u, lo[v] + v, o_axis + t), permuted to x, y, z;
+ *   second moments about the local origin
+ *     Euu = A h (hu^2 S4 + hu^2/3 S0), Evv likewise with S5, Ett = A h^3/3 S6,
+ *     Euv = A h hu hv S7, Eut = A h^2/2 hu S8, Evt = A h^2/2 hv S9;
+ *   central moments Cab = Eab - V a b;  inertia = trace(C) 1 - C.
+ * S0 = 0: volume 0, the centroid is the box's centre, the inertia 0.
+ * projected_area = rays_hit A; cell = (2hu, 2hv, h).  -1 for a bad grid. */
+int wo_mass_properties_from_sums(Wo_MassGrid const* grid, Wo_MassSums const* sums, Wo_MassProperties* out);
+/* Adds the sums of the grid's row range into *d_sums: device memory, 8-byte
+ * aligned, zeroed by the caller before the first part.  Several row ranges, or
+ * several renderers on several devices, may so accumulate one grid: the sum of the
+ * parts is the whole, bit for bit.  Asynchronous on `stream` and ordered as
+ * wo_renderer_trace_spans_device is (an edited scene is compiled and uploaded
+ * first); always the interpreter's sweep.  -1 on a device-less renderer. */
+int wo_renderer_mass_sums_device(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_MassSums* d_sums, void* stream);
+/* The host form: zeroes a device buffer, runs the row range the grid names, copies
+ * the sums back (also to *sums_or_null) and finalises them (synchronous). */
+int wo_renderer_mass_properties(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_MassProperties* out,
+                                Wo_MassSums* sums_or_null);
+
 /* Path-tracer kernel selection (results are identical; only speed differs).
  *   AUTO         union-only scenes of more than WOLOLO_LANES_MIN_PRIMS (256)
  *                primitives -> LANES; else scenes of up to WOLOLO_JIT_MAX_PRIMS
@@ -429,7 +515,7 @@ void wo_renderer_clear_error(void);
 /* sizeof(type) (field NULL) or offsetof(type, field) as this library was
  * compiled, for the value types of the C ABI (Wo_Vec3, Wo_Quaternion,
  * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame, Wo_Ray, Wo_RayHit,
- * Wo_RayCrossing, Wo_RaySpans);
+ * Wo_RayCrossing, Wo_RaySpans, Wo_MassGrid, Wo_MassPlan, Wo_MassSums, Wo_MassProperties);
  * (size_t)-1 for an unknown name.  Bindings check their mirrors with it. */
 size_t wo_abi_layout(char const* type, char const* field);
 /* Device self-check of the path tracer's fast correctly rounded square root
