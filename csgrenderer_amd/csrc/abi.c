@@ -53,6 +53,8 @@ static const AbiField kAbi[] = {
     T(Wo_MassProperties), F(Wo_MassProperties, volume), F(Wo_MassProperties, centroid), F(Wo_MassProperties, inertia),
     F(Wo_MassProperties, projected_area), F(Wo_MassProperties, cell), F(Wo_MassProperties, rays),
     F(Wo_MassProperties, crossings),
+    T(Wo_FeatureIds), F(Wo_FeatureIds, node), F(Wo_FeatureIds, leaf), F(Wo_FeatureIds, material),
+    F(Wo_FeatureIds, flags),
 };
 
 #undef T

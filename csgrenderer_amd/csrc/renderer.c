@@ -941,6 +941,74 @@ int wo_renderer_mass_properties(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_Mass
     return wo_mass_properties_from_sums(grid, &sums, out);
 }
 
+/* first-hit feature buffers: every argument is checked before the device is touched, so a
+ * device-less renderer reports a bad argument by its own message */
+_Static_assert(sizeof(Wo_FeatureIds) == 16, "a Wo_FeatureIds is one 16-byte row");
+
+static int features_args(Wo_Renderer* r, Wo_RenderParams const* p, void const* buf, size_t plane_stride,
+                         uint32_t tile_rows, uint32_t rank, uint32_t nranks) {
+    if (!p) {
+        wo_set_error("render_features: NULL params");
+        return -1;
+    }
+    if (p->width == 0u || p->height == 0u || p->spp == 0u) {
+        wo_set_error("render_features: width, height and spp must not be 0 (%ux%u, spp %u)", p->width, p->height, p->spp);
+        return -1;
+    }
+    if (p->mode != (uint32_t)WO_SHADING_PATHTRACE) {
+        wo_set_error("render_features: mode %u is not WO_SHADING_PATHTRACE (the planes are those of a path-traced frame)",
+                     p->mode);
+        return -1;
+    }
+    if (nranks == 0u || rank >= nranks || tile_rows == 0u) {
+        wo_set_error("render_features: bad row tiling (tile_rows=%u rank=%u nranks=%u)", tile_rows, rank, nranks);
+        return -1;
+    }
+    const uint32_t local_rows = wo_rank_local_rows_ex(p->height, tile_rows, nranks, nranks > 1u ? r->band_cycle : 0u,
+                                                      nranks > 1u ? r->band_skip : 0u);
+    if (plane_stride < (size_t)local_rows * p->width) {
+        wo_set_error("render_features: plane_stride %zu is short of the rank's %u rows x %u pixels", plane_stride,
+                     local_rows, p->width);
+        return -1;
+    }
+    if (!buf || ((uintptr_t)buf & 15u)) {
+        wo_set_error("render_features: the buffer is NULL or not 16-byte aligned");
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_render_features_device(Wo_Renderer* r, Wo_RenderParams const* params, void* d_out, size_t plane_stride,
+                                       uint32_t tile_rows, uint32_t rank, uint32_t nranks, void* stream) {
+    if (!r) return -1;
+    if (features_args(r, params, d_out, plane_stride, tile_rows, rank, nranks)) return -1;
+    if (sync_device(r)) return -1;
+    WoFrame fr;
+    if (wo_renderer_frame_desc(r, params, tile_rows, rank, nranks, &fr)) return -1;
+    char err[256] = {0};
+    if (wo_dev_features(r->dev, &fr, d_out, plane_stride, r->ray_tracer, stream, err, sizeof err)) {
+        wo_set_error("feature launch failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_render_features(Wo_Renderer* r, Wo_RenderParams const* params, void* out) {
+    if (!r) return -1;
+    /* one rank, one band of the frame's height: the local rows are the frame's */
+    const uint32_t tile_rows = params && params->height ? params->height : 1u;
+    if (features_args(r, params, out, params ? (size_t)params->width * params->height : 0u, tile_rows, 0u, 1u)) return -1;
+    if (sync_device(r)) return -1;
+    WoFrame fr;
+    if (wo_renderer_frame_desc(r, params, tile_rows, 0u, 1u, &fr)) return -1;
+    char err[256] = {0};
+    if (wo_dev_features_host(r->dev, &fr, out, r->ray_tracer, err, sizeof err)) {
+        wo_set_error("feature query failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
 /* oracle.c normalize3 / sqrt_pt, one rounding per operation (-ffp-contract=off) */
 static void normalize3f(float v[3]) {
     const float dot = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];

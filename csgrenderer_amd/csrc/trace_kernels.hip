@@ -1372,6 +1372,276 @@ __global__ __launch_bounds__(kBlock, kMode == 2 ? WO_LANES_BVH_MIN_WAVES : WO_LA
 }
 
 // ---------------------------------------------------------------------------
+// First-hit feature buffers (wo_renderer_render_features_device): per pixel the mean
+// albedo, facing normal and depth of the first hits of the frame's own camera rays,
+// the coverage, and the ids under the pixel centre (renderer_ext.h states the
+// semantics).  No ray is read: a lane makes sample s of its pixel in registers, as
+// pathtrace_block's job_ray does, traces it and adds to seven exact 32.32 sums and a
+// hit count that stay in registers; it then stores one 16-byte row per plane.  The
+// only other global traffic is the program, the materials and the node table.
+// ---------------------------------------------------------------------------
+struct FeatureLaunch {
+    WoFrame fr;
+    const WoMaterial* __restrict__ mats;
+    const uint32_t* __restrict__ nodes;  // per program record: its source node handle
+    uint4* __restrict__ out;
+    uint64_t plane_stride;               // 16-byte rows between two planes
+    uint32_t local_rows, n_mats;
+};
+
+// The camera ray of sample s of frame pixel (x, y): job_ray (wo_device_common.h) and the
+// unit3 that follows its take, restated for one pixel per lane.  `centre`: the pixel
+// centre without jitter or lens, the NORMALS sample (wo_renderer_pixel_ray).
+__device__ __forceinline__ void feature_ray(const WoFrame& fr, uint32_t seed_hash, uint32_t x, uint32_t y, uint32_t s,
+                                            bool centre, F3& o, F3& d) {
+    const WoCamera& cam = fr.cam;
+    Rng nr;
+    nr.s = pcg_hash((y * fr.width + x) ^ pcg_hash((fr.sample_offset + s) ^ seed_hash));
+    float sx, ty;
+    if (centre) {
+        sx = ((float)x + 0.5f) * fr.inv_width;
+        ty = ((float)(fr.height - 1u - y) + 0.5f) * fr.inv_height;
+    } else {
+        float r1 = nr.uniform();
+        float r2 = nr.uniform();
+        sx = ((float)x + r1) * fr.inv_width;
+        ty = ((float)(fr.height - 1u - y) + r2) * fr.inv_height;
+    }
+    float offx = 0.0f, offy = 0.0f, offz = 0.0f;
+    if (cam.lens_radius > 0.0f && !centre) {
+        // uniform point on the unit disk: radius sqrt(u), angle 2*pi*v
+        float rr = sqrt_pt(nr.uniform());
+        float sn, cs;
+        sincos_turns(nr.uniform(), sn, cs);
+        float px = rr * cs, py = rr * sn;
+        float rx = cam.lens_radius * px, ry = cam.lens_radius * py;
+        offx = cam.u[0] * rx + cam.v[0] * ry;
+        offy = cam.u[1] * rx + cam.v[1] * ry;
+        offz = cam.u[2] * rx + cam.v[2] * ry;
+    }
+    o = f3(cam.origin[0] + offx, cam.origin[1] + offy, cam.origin[2] + offz);
+    d = unit3(f3(((cam.lower_left[0] + sx * cam.horizontal[0]) + ty * cam.vertical[0]) - cam.origin[0] - offx,
+                 ((cam.lower_left[1] + sx * cam.horizontal[1]) + ty * cam.vertical[1]) - cam.origin[1] - offy,
+                 ((cam.lower_left[2] + sx * cam.horizontal[2]) + ty * cam.vertical[2]) - cam.origin[2] - offz));
+}
+
+// A pixel's sums: albedo, facing normal (0 on a miss) and the hits' t, each sample
+// quantised as the frame's radiance is, so the means do not depend on sample order.
+struct FeatureSums {
+    long long a[3], n[3], t;
+    uint32_t hits;
+};
+
+// One sample's first hit (`L`: the hit member's leaf record) or miss added to the sums.
+__device__ __forceinline__ void feature_add(FeatureSums& fs, const FeatureLaunch& fl, bool found, const Hit& h,
+                                            const WoRec& L, F3 o, F3 d) {
+    F3 a;
+    if (found) {
+        const F3 P = f3(o.x + h.t * d.x, o.y + h.t * d.y, o.z + h.t * d.z);
+        F3 n;
+        if (L.op == WO_LEAF_SPHERE)
+            n = f3((P.x - L.f[0]) * L.f[4], (P.y - L.f[1]) * L.f[4], (P.z - L.f[2]) * L.f[4]);
+        else
+            n = f3(L.f[0], L.f[1], L.f[2]);
+        const F3 N = h.type() == 0u ? n : f3(-n.x, -n.y, -n.z);
+        const F3 ns = h.root_after != 0u ? N : f3(-N.x, -N.y, -N.z);
+        const WoMaterial m = fl.mats[L.u0 < fl.n_mats ? L.u0 : 0u];
+        const bool diel = (m.kind != WO_MAT_LAMBERTIAN) & (m.kind != WO_MAT_METAL);
+        a = diel ? f3(1.0f, 1.0f, 1.0f) : f3(m.albedo[0], m.albedo[1], m.albedo[2]);
+        fs.n[0] += quantize_radiance(ns.x);
+        fs.n[1] += quantize_radiance(ns.y);
+        fs.n[2] += quantize_radiance(ns.z);
+        fs.t += quantize_radiance(h.t);
+        ++fs.hits;
+    } else {
+        a = sky(d);
+    }
+    fs.a[0] += quantize_radiance(a.x);
+    fs.a[1] += quantize_radiance(a.y);
+    fs.a[2] += quantize_radiance(a.z);
+}
+
+// The pixel's three rows: plane p of local pixel i is row p * plane_stride + i.
+__device__ __forceinline__ void feature_store(const FeatureLaunch& fl, size_t i, const FeatureSums& fs, uint4 ids) {
+    const uint32_t spp = fl.fr.spp;
+    const float cover = (float)((double)fs.hits / (double)spp);
+    const float depth = fs.hits ? mean_radiance(fs.t, fs.hits) : kInf;
+    float4* out = reinterpret_cast<float4*>(fl.out);
+    out[i] = make_float4(mean_radiance(fs.a[0], spp), mean_radiance(fs.a[1], spp), mean_radiance(fs.a[2], spp), cover);
+    out[fl.plane_stride + i] =
+        make_float4(mean_radiance(fs.n[0], spp), mean_radiance(fs.n[1], spp), mean_radiance(fs.n[2], spp), depth);
+    fl.out[2u * fl.plane_stride + i] = ids;
+}
+
+// Wo_FeatureIds of the centre ray's result (leaf = the hit member's record index).
+__device__ __forceinline__ uint4 feature_ids(const FeatureLaunch& fl, bool found, const Hit& h, const WoRec& L,
+                                             uint32_t leaf) {
+    if (!found) return make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0u);
+    const uint32_t flags = kRayHit | (h.type() ? kRayExit : 0u) | (h.root_after ? kRayEnters : 0u);
+    return make_uint4(fl.nodes[leaf], leaf, L.u0 < fl.n_mats ? L.u0 : 0u, flags);
+}
+
+// A wave's item of 64 pixels of the rank's local rows: an 8 x 8 tile (lane = 8 row +
+// column) or a 64 x 1 strip of one row, numbered row-major and dealt to the waves by
+// the grid-stride loop.  Both were measured; the planes do not depend
+// on the footprint.
+template <bool kTile>
+struct FeatureItems {
+    uint32_t across;
+    uint64_t count;
+    __device__ __forceinline__ FeatureItems(uint32_t width, uint32_t rows) {
+        across = kTile ? (width + 7u) >> 3 : (width + 63u) >> 6;
+        count = (uint64_t)across * (kTile ? (rows + 7u) >> 3 : rows);
+    }
+    __device__ __forceinline__ void pixel(uint64_t item, uint32_t lane, uint32_t& lx, uint32_t& lrow) const {
+        const uint32_t iy = (uint32_t)(item / across), ix = (uint32_t)(item - (uint64_t)iy * across);
+        lx = ix * (kTile ? 8u : 64u) + (kTile ? (lane & 7u) : lane);
+        lrow = iy * (kTile ? 8u : 1u) + (kTile ? (lane >> 3) : 0u);
+    }
+};
+
+// The interpreter over the frame's camera rays (any scene): the wave traces sample s
+// of its 64 pixels together, which suits the wave-uniform walk as camera waves suit
+// the frame kernel.  A lane whose pixel is outside the frame (past the right edge, or
+// a local row beyond the frame's last) traces the wave's first in-frame pixel and
+// drops the result; a wave without an in-frame pixel skips the item.
+template <bool kProgInLds, bool kTile>
+__global__ __launch_bounds__(kBlock) void features_kernel(const WoRec* __restrict__ gprog, uint32_t nrec, KLayout lay,
+                                                          FeatureLaunch fl) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uni(tid >> 6);
+
+    uint32_t* scratch = smem;
+    InterpTracer<false> tr;
+    if constexpr (kProgInLds) {
+        const uint4* src = reinterpret_cast<const uint4*>(gprog);
+        uint4* dst = reinterpret_cast<uint4*>(smem);
+        for (uint32_t i = tid; i < nrec * 2u; i += kBlock) dst[i] = src[i];
+        __syncthreads();
+        tr.prog.p = reinterpret_cast<const WoRec*>(smem);
+        scratch = smem + nrec * 8u;
+    } else {
+        tr.prog.p = gprog;
+    }
+    uint32_t* ws = scratch + wave * lay.wave_words;
+    tr.nrec = nrec;
+    tr.codes = ws;
+    tr.ordpc = ws + lay.ordpc_off;
+    tr.hib = ws + lay.hib_off;
+    tr.lane = lane;
+
+    const uint32_t W = fl.fr.width, H = fl.fr.height, spp = fl.fr.spp;
+    const uint32_t seed_hash = pcg_hash(fl.fr.seed);
+    const FeatureItems<kTile> items(W, fl.local_rows);
+    const uint64_t stride = (uint64_t)gridDim.x * (kBlock / 64u);
+    for (uint64_t item = (uint64_t)blockIdx.x * (kBlock / 64u) + wave; item < items.count; item += stride) {
+        uint32_t lx, lrow;
+        items.pixel(item, lane, lx, lrow);
+        const uint32_t gy = lrow < fl.local_rows ? local_to_global_row(fl.fr, lrow) : H;
+        const bool in = lx < W && gy < H;
+        const uint64_t vm = __ballot(in);
+        if (vm == 0ull) continue;
+        const int src = __builtin_ctzll(vm);
+        const uint32_t x = in ? lx : (uint32_t)__builtin_amdgcn_readlane((int)lx, src);
+        const uint32_t y = in ? gy : (uint32_t)__builtin_amdgcn_readlane((int)gy, src);
+        FeatureSums fs = {};
+        uint4 ids = make_uint4(0u, 0u, 0u, 0u);
+        // samples 0 .. spp - 1, then the centre ray (one call site of the tracer; ends for every spp)
+        for (uint32_t s = 0;; ++s) {
+            const bool centre = s == spp;
+            F3 o, d;
+            feature_ray(fl.fr, seed_hash, x, y, s, centre, o, d);
+            Hit h;
+            h.t = kInf;
+            h.lo = 0;
+            h.root_after = 0;
+            const bool found = tr.trace(o, d, h);
+            WoRec L = {};
+            uint32_t leaf = 0;
+            if (found) {
+                leaf = tr.ordpc[h.ord()] + 1u + h.member();
+                L = tr.prog[leaf];
+            }
+            if (centre) {
+                ids = feature_ids(fl, found, h, L, leaf);
+                break;
+            }
+            feature_add(fs, fl, found, h, L, o, d);
+        }
+        if (in) feature_store(fl, (size_t)lrow * W + lx, fs, ids);
+    }
+}
+
+// The lane tracer's ordered BVH walk over the same rays (union-only scenes; forms 2
+// and 3, trace_rays_lanes_kernel's prologue).  Every lane walks on its own, so a lane
+// whose pixel is outside the frame does nothing.  Five and six waves per SIMD, not the
+// ray kernels' seven and eight: the sums are 15 registers the walk does not have, and
+// under the ray kernels' bounds (72 / 64 VGPRs) they spill 72 bytes of scratch per lane.
+template <int kMode, bool kTile>
+__global__ __launch_bounds__(kBlock, kMode == 2 ? 5 : 6) void features_lanes_kernel(
+    const WoRec* __restrict__ prog, const uint32_t* __restrict__ ordpc, LaneBvh bvh, FeatureLaunch fl) {
+    static_assert(kMode == 2 || kMode == 3, "feature buffers walk the union-only forms");
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    LaneTracer<kMode, false> tr;
+    tr.prog = prog;
+    tr.ordpc = ordpc;
+    tr.lnodes = bvh.nodes;
+    tr.lgeo = bvh.geo;
+    tr.lkind = bvh.kind;
+    tr.ltrec = bvh.trec;
+    tr.lleaf = bvh.leaves;
+    tr.nalways = bvh.nalways;
+    tr.lroot = bvh.root;
+    tr.nprims = bvh.nprims;
+    tr.stk = smem + threadIdx.x;
+    tr.stk16 = reinterpret_cast<uint16_t*>(smem) + threadIdx.x;
+    {
+        // the top levels of the BVH next to the stacks, as pathtrace_lanes_kernel lays them out
+        float4* top = reinterpret_cast<float4*>(smem + ((bvh.depth * kBlock + 3u) & ~3u));
+        for (uint32_t i = threadIdx.x; i < 4u * bvh.ntop; i += kBlock) top[i] = bvh.nodes[i];
+        tr.ltop = (typename LaneTracer<kMode, false>::LdsNodes)top;
+        tr.ntop = bvh.ntop;
+    }
+    __syncthreads();
+
+    const uint32_t W = fl.fr.width, H = fl.fr.height, spp = fl.fr.spp;
+    const uint32_t seed_hash = pcg_hash(fl.fr.seed);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const FeatureItems<kTile> items(W, fl.local_rows);
+    const uint64_t stride = (uint64_t)gridDim.x * (kBlock / 64u);
+    for (uint64_t item = (uint64_t)blockIdx.x * (kBlock / 64u) + wave; item < items.count; item += stride) {
+        uint32_t x, lrow;
+        items.pixel(item, lane, x, lrow);
+        const uint32_t y = lrow < fl.local_rows ? local_to_global_row(fl.fr, lrow) : H;
+        if (!(x < W && y < H)) continue;
+        FeatureSums fs = {};
+        uint4 ids = make_uint4(0u, 0u, 0u, 0u);
+        for (uint32_t s = 0;; ++s) {
+            const bool centre = s == spp;
+            F3 o, d;
+            feature_ray(fl.fr, seed_hash, x, y, s, centre, o, d);
+            Hit h;
+            h.t = kInf;
+            h.lo = 0;
+            h.root_after = 0;
+            const bool found = tr.trace(o, d, h);
+            WoRec L = {};
+            uint32_t leaf = 0;
+            if (found) {
+                leaf = ordpc[h.ord()] + 1u + h.member();
+                L = prog[leaf];
+            }
+            if (centre) {
+                ids = feature_ids(fl, found, h, L, leaf);
+                break;
+            }
+            feature_add(fs, fl, found, h, L, o, d);
+        }
+        feature_store(fl, (size_t)lrow * W + x, fs, ids);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Ray span queries (wo_renderer_trace_spans_device): the interpreter's sweep carried
 // on past the first flip of the root.  Every flip in (WO_T_MIN, t_max] is a crossing;
 // a ray's summary is Wo_RaySpans (count, flags, length, stored: one uint4), a crossing
@@ -2499,6 +2769,20 @@ static const void* ray_kernel(PathKind kind) {
     default: return nullptr;
     }
 }
+// a feature launch's kernel: the ray kernels' forms, each for 8 x 8 tiles or 64 x 1 strips
+template <bool kTile>
+static const void* feature_kernel_of(PathKind kind) {
+    switch (kind) {
+    case kLanesBvh: return (const void*)features_lanes_kernel<2, kTile>;
+    case kLanesBvhSpheres: return (const void*)features_lanes_kernel<3, kTile>;
+    case kInterpLds: return (const void*)features_kernel<true, kTile>;
+    case kInterpGlobal: return (const void*)features_kernel<false, kTile>;
+    default: return nullptr;
+    }
+}
+static const void* feature_kernel(PathKind kind, bool tile) {
+    return tile ? feature_kernel_of<true>(kind) : feature_kernel_of<false>(kind);
+}
 // a span launch's kernel: the program in LDS or not, the sweep's window 4, 8 or 16 keys wide
 template <bool kProgInLds>
 static const void* span_kernel_of(int window) {
@@ -2837,6 +3121,107 @@ extern "C" int wo_dev_trace_rays_host(WoDev* dev, void const* rays, void* hits, 
     if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
     if (e != hipSuccess) {
         set_err(err, errlen, "ray query", e);
+        return -1;
+    }
+    return 0;
+}
+
+// ---- first-hit feature buffers ----
+
+// The wave's footprint (DESIGN 3.12 holds the measurement; the planes do not depend on
+// it): WOLOLO_FEATURE_TILE = 8x8 | 64x1.
+static bool feature_tile() {
+    const char* v = getenv("WOLOLO_FEATURE_TILE");
+    return !(v && strcmp(v, "64x1") == 0);
+}
+
+extern "C" int wo_dev_features(WoDev* dev, WoFrame const* frame, void* d_out, size_t plane_stride, int form,
+                               void* stream_v, char* err, size_t errlen) {
+    hipStream_t stream = (hipStream_t)stream_v;  // NULL = the null stream (HIP convention)
+    if (!dev->d_prog || !dev->d_nodes || dev->n_nodes != dev->n_recs) {
+        snprintf(err, errlen, "no scene (or no node table) on the device");
+        return -1;
+    }
+    FeatureLaunch fl;
+    fl.fr = *frame;
+    if (fl.fr.width == 0 || fl.fr.height == 0 || fl.fr.spp == 0 || fl.fr.tile_rows == 0 || fl.fr.nranks == 0 ||
+        fl.fr.rank >= fl.fr.nranks) {
+        snprintf(err, errlen, "bad frame (%ux%u, spp=%u, tile_rows=%u rank=%u nranks=%u)", fl.fr.width, fl.fr.height,
+                 fl.fr.spp, fl.fr.tile_rows, fl.fr.rank, fl.fr.nranks);
+        return -1;
+    }
+    if (fl.fr.n_recs != dev->n_recs || fl.fr.n_prims != dev->n_prims) {
+        snprintf(err, errlen, "frame/scene mismatch (recs %u vs %u)", fl.fr.n_recs, dev->n_recs);
+        return -1;
+    }
+    fl.local_rows = wo_rank_local_rows_ex(fl.fr.height, fl.fr.tile_rows, fl.fr.nranks, fl.fr.band_cycle, fl.fr.band_skip);
+    if (!d_out || ((uintptr_t)d_out & 15u) || plane_stride < (size_t)fl.local_rows * fl.fr.width) {
+        snprintf(err, errlen, "the planes' buffer must be device memory, 16-byte aligned, plane_stride >= %zu rows",
+                 (size_t)fl.local_rows * fl.fr.width);
+        return -1;
+    }
+    if (dev->n_prims >= (1u << 20)) {
+        snprintf(err, errlen, "scene has %u primitives (max %u)", dev->n_prims, (1u << 20) - 1u);
+        return -1;
+    }
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    fl.mats = dev->d_mats;
+    fl.nodes = dev->d_nodes;
+    fl.out = (uint4*)d_out;
+    fl.plane_stride = plane_stride;
+    fl.n_mats = dev->n_mats;
+    // the kernel family of the ray queries (wo_dev_trace_rays)
+    const WoLaneBvhDesc& lb = dev->lbvh;
+    const bool lanes = form != 1 && lb.union_only && !lb.stack16;
+    PathKind kind;
+    size_t dyn_lds = 0;
+    KLayout lay = {};
+    if (lanes) {
+        kind = lb.spheres_only ? kLanesBvhSpheres : kLanesBvh;
+        dyn_lds = lane_bvh_lds(lb);
+    } else if (interp_plan(dev->n_recs, dev->n_prims, &lay, &kind, &dyn_lds, err, errlen)) {
+        return -1;
+    }
+    const bool tile = feature_tile();
+    const void* kernel = feature_kernel(kind, tile);
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, dyn_lds);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    // one item (tile or strip) per wave: ray_grid's count for as many lanes
+    const uint64_t items = tile ? (uint64_t)((fl.fr.width + 7u) / 8u) * ((fl.local_rows + 7u) / 8u)
+                                : (uint64_t)((fl.fr.width + 63u) / 64u) * fl.local_rows;
+    LaneBvh bvh = lane_bvh(dev);
+    void* lane_args[] = {&dev->d_prog, &dev->d_ordpc, &bvh, &fl};
+    void* interp_args[] = {&dev->d_prog, &dev->n_recs, &lay, &fl};
+    (void)hipLaunchKernel(kernel, dim3(ray_grid(dev, (size_t)(items * 64u), per_cu)), dim3(kBlock),
+                          lanes ? lane_args : interp_args, dyn_lds, stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_err(err, errlen, "feature kernel launch", e);
+        return -1;
+    }
+    dev->ray_kind = (uint32_t)kind;
+    dev->ray_last = true;
+    return 0;
+}
+
+extern "C" int wo_dev_features_host(WoDev* dev, WoFrame const* frame, void* out, int form, char* err, size_t errlen) {
+    hipError_t e = hipSetDevice(dev->device);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "hipSetDevice", e);
+        return -1;
+    }
+    const size_t pixels = (size_t)frame->width * frame->height, bytes = 3u * pixels * sizeof(float4);
+    if (ensure_buffer(&dev->d_rayio, &dev->rayio_cap, bytes, err, errlen)) return -1;
+    if (wo_dev_features(dev, frame, dev->d_rayio, pixels, form, dev->stream, err, errlen)) return -1;
+    e = hipMemcpyAsync(out, dev->d_rayio, bytes, hipMemcpyDeviceToHost, dev->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+    if (e != hipSuccess) {
+        set_err(err, errlen, "feature query", e);
         return -1;
     }
     return 0;

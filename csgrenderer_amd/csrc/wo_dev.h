@@ -113,6 +113,15 @@ typedef struct WoMassLaunch {
 } WoMassLaunch;
 int wo_dev_mass_sums(WoDev* dev, WoMassLaunch const* ml, void* d_sums, void* stream, char* err, size_t errlen);
 int wo_dev_mass_sums_host(WoDev* dev, WoMassLaunch const* ml, void* sums, char* err, size_t errlen);
+/* First-hit feature buffers (renderer_ext.h wo_renderer_render_features_device): the
+ * three planes of the rank's rows of `frame` into d_out (device memory, 16-byte
+ * aligned; plane p of local pixel i is the 16-byte row p * plane_stride + i), async on
+ * `stream`.  `form` is a Wo_RayTracer, as for wo_dev_trace_rays.  The host form renders
+ * the whole frame (one rank, frame->tile_rows = its height) with the planes contiguous
+ * and copies the 3 * width * height rows back (synchronous). */
+int wo_dev_features(WoDev* dev, WoFrame const* frame, void* d_out, size_t plane_stride, int form, void* stream,
+                    char* err, size_t errlen);
+int wo_dev_features_host(WoDev* dev, WoFrame const* frame, void* out, int form, char* err, size_t errlen);
 /* Per program record its source node handle (Wo_Renderer::prog_nodes), read by the
  * ray kernels; uploaded with the scene (blocking, after wo_dev_upload_scene). */
 int wo_dev_upload_nodes(WoDev* dev, uint32_t const* nodes, uint32_t n_recs, char* err, size_t errlen);

@@ -139,6 +139,17 @@ class MassProperties(Structure):
 MASS_MAX_CELLS = 32768
 assert ctypes.sizeof(MassGrid) == 48 and ctypes.sizeof(MassSums) == 192
 
+
+# renderer_ext.h Wo_FeatureIds and the planes of wo_renderer_render_features[_device]
+class FeatureIds(Structure):
+    _fields_ = [("node", c_uint32), ("leaf", c_uint32), ("material", c_uint32), ("flags", c_uint32)]
+
+
+# numpy view of the ids plane (Renderer.render_features returns it)
+FEATURE_IDS_FIELDS = [("node", "<u4"), ("leaf", "<u4"), ("material", "<u4"), ("flags", "<u4")]
+FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_IDS, FEATURE_PLANES = 0, 1, 2, 3
+assert ctypes.sizeof(FeatureIds) == 16
+
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 32
 assert ctypes.sizeof(RayCrossing) == 16 and ctypes.sizeof(RaySpans) == 16
 assert ctypes.sizeof(Vec3) == 24 and ctypes.sizeof(Quaternion) == 32 and ctypes.sizeof(NodeArgument) == 64
@@ -224,6 +235,9 @@ SIGNATURES = {
     "wo_mass_properties_from_sums": (c_int, [POINTER(MassGrid), POINTER(MassSums), POINTER(MassProperties)]),
     "wo_renderer_mass_sums_device": (c_int, [c_void_p, POINTER(MassGrid), c_void_p, c_void_p]),
     "wo_renderer_mass_properties": (c_int, [c_void_p, POINTER(MassGrid), POINTER(MassProperties), POINTER(MassSums)]),
+    "wo_renderer_render_features_device": (c_int, [c_void_p, POINTER(RenderParams), c_void_p, c_size_t, c_uint32,
+                                                   c_uint32, c_uint32, c_void_p]),
+    "wo_renderer_render_features": (c_int, [c_void_p, POINTER(RenderParams), c_void_p]),
     "wo_renderer_set_jit_async": (None, [c_void_p, c_int]),
     "wo_renderer_jit_pending": (c_int, [c_void_p]),
     "wo_renderer_prepare": (c_int, [c_void_p]),
@@ -563,6 +577,27 @@ class Renderer:
         if self.lib.wo_renderer_mass_properties(self.ptr, ctypes.byref(grid), ctypes.byref(props), ctypes.byref(sums)):
             raise WololoError(last_error())
         return props, sums
+
+    # ---- first-hit feature buffers (renderer_ext.h wo_renderer_render_features ...) ----
+    def render_features(self, params: RenderParams):
+        """The feature planes of a PATHTRACE frame: (albedo (H, W, 4) float32 with w = coverage,
+        normal (H, W, 4) float32 with w = mean hit depth, ids (H, W) FEATURE_IDS_FIELDS).  Synchronous."""
+        import numpy as np
+        h, w = int(params.height), int(params.width)
+        out = np.zeros((FEATURE_PLANES, h, w, 4), dtype=np.float32)
+        if self.lib.wo_renderer_render_features(self.ptr, ctypes.byref(params), out.ctypes.data_as(c_void_p)):
+            raise WololoError(last_error())
+        ids = out[FEATURE_IDS].view(np.uint32).reshape(h, w, 4).view(np.dtype(FEATURE_IDS_FIELDS)).reshape(h, w)
+        return out[FEATURE_ALBEDO], out[FEATURE_NORMAL], ids
+
+    def render_features_device(self, params: RenderParams, d_out: int, plane_stride: int, tile_rows: int, rank: int,
+                               nranks: int, stream: int = 0):
+        """This rank's rows of the three planes into device memory at d_out (plane p of local pixel i
+        is the 16-byte row p * plane_stride + i), asynchronously on `stream`."""
+        if self.lib.wo_renderer_render_features_device(self.ptr, ctypes.byref(params) if params is not None else None,
+                                                       c_void_p(d_out or None), int(plane_stride), tile_rows, rank,
+                                                       nranks, c_void_p(stream or None)):
+            raise WololoError(last_error())
 
     def frame_desc(self, params: RenderParams, tile_rows=16, rank=0, nranks=1) -> WoFrame:
         fr = WoFrame()

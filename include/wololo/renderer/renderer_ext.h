@@ -420,6 +420,85 @@ int wo_renderer_mass_sums_device(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_Mas
 int wo_renderer_mass_properties(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_MassProperties* out,
                                 Wo_MassSums* sums_or_null);
 
+/* ---- first-hit feature buffers (albedo, normal, depth, coverage, ids) of a frame ----
+ * The guide layers of a path-traced frame, made from the rays that frame shoots: per
+ * pixel the mean first-hit albedo, facing normal and depth over the frame's own camera
+ * samples (sub-pixel jitter and lens offsets included, so the planes line up with the
+ * noisy frame at edges and under defocus), the coverage, and the node under the pixel
+ * centre.  A separate pass of spp + 1 camera-ray traces per pixel; exact 32.32 sums make
+ * every value independent of launch geometry, and a CPU reference matches bit for bit.
+ *
+ * For Wo_RenderParams {width W, height H, spp, seed, sample_offset}, mode =
+ * WO_SHADING_PATHTRACE (max_depth and time_sec are ignored), sample s, 0 <= s < spp, of
+ * pixel (x, y) (row 0 = top) is the camera ray of the path tracer (oracle.c shade_pixel),
+ * every operation fp32 and rounded once, in this order:
+ *   rng = pcg(y W + x ^ pcg((sample_offset + s) ^ pcg(seed)));  jx, jy = two draws of rng;
+ *   u = ((float)x + jx) * inv_width;  v = ((float)(H - 1 - y) + jy) * inv_height;
+ *   off = 0, or with lens_radius > 0 two more draws: rad = sqrt_pt(draw), (s, c) =
+ *     sincos_turn(draw), rx = lens_radius * (rad c), ry = lens_radius * (rad s),
+ *     off = cam.u * rx + cam.v * ry;
+ *   o = origin + off;  d = normalize(((lower_left + u horizontal) + v vertical) - origin - off)
+ * with the camera as wo_renderer_frame_desc resolves it.  Its first hit h is the tracer's
+ * segment query (what wo_renderer_trace_rays reports with t_max = +INFINITY), so a
+ * sample's hit / miss and t are those of the path-traced frame's first segment for the
+ * same parameters.  With L the hit member's leaf record:
+ *   facing normal ns: the leaf's outward normal at o + t d, negated for WO_RAY_EXIT and
+ *     negated again without WO_RAY_ENTERS -- Wo_RayHit.normal;
+ *   albedo a: m = materials[L.u0 < n_materials ? L.u0 : 0]; m.albedo for a lambertian or
+ *     a metal, (1, 1, 1) for a dielectric;
+ *   a miss: a = the sky's colour along d (the radiance that sample adds to the frame),
+ *     ns = 0, no depth.
+ * With Q(v) = (int64)((double)v * 2^32) (0 for |v| >= 2^20 or NaN) and M(sum, n) =
+ * (float)(((double)sum * 2^-32) / (double)n), the frame's own accumulation, and `hits` the
+ * samples that hit:
+ *   plane WO_FEATURE_ALBEDO, float4: rgb[i] = M(sum_s Q(a_i), spp);  w = coverage =
+ *     (float)((double)hits / (double)spp);
+ *   plane WO_FEATURE_NORMAL, float4: xyz[i] = M(sum_s Q(ns_i), spp) -- misses add 0, so
+ *     its length falls with the coverage;  w = depth = M(sum_{hits} Q(t), hits), or
+ *     +INFINITY when hits = 0;
+ *   plane WO_FEATURE_IDS, Wo_FeatureIds: the pixel-CENTRE ray, the one
+ *     wo_renderer_pixel_ray returns (no jitter, no lens, t_max = +INFINITY): node, leaf
+ *     and material as in Wo_RayHit, flags = its WO_RAY_* (0xFFFFFFFF x 3 and flags = 0 on
+ *     a miss) -- wo_renderer_pick(params, x, y) field for field, for every pixel at once;
+ *     one more ray per pixel, the same for every spp and sample_offset.
+ * The sums are exact while a pixel's sum of |v| stays below 2^31 (as the frame's are).
+ * Progressive accumulation is not kept: average batches of disjoint sample_offset
+ * ranges in float. */
+#define WO_FEATURE_ALBEDO 0u   /* rgb = mean first-hit albedo (sky on a miss), w = coverage */
+#define WO_FEATURE_NORMAL 1u   /* xyz = mean facing normal, w = mean hit depth (+inf: no hit) */
+#define WO_FEATURE_IDS    2u   /* Wo_FeatureIds of the pixel-centre ray */
+#define WO_FEATURE_PLANES 3u
+typedef struct Wo_FeatureIds {   /* 16 bytes */
+    Wo_Node node;
+    uint32_t leaf;
+    Wo_Material material;
+    uint32_t flags;
+} Wo_FeatureIds;
+
+/* This rank's rows of the three planes into DEVICE memory d_out (16-byte aligned):
+ * plane p of the rank-local pixel (lrow, x) is the 16-byte row p * plane_stride +
+ * lrow * width + x.  plane_stride counts 16-byte rows and is at least local_rows * width,
+ * local_rows = wo_rank_local_rows[_ex](height, tile_rows, nranks[, band weight]); rows of
+ * a plane beyond local_rows * width are not written, nor are local rows past the frame's
+ * last row.  The rank's rows and their order are exactly those of
+ * wo_renderer_render_rows_device with the same tile_rows, rank and nranks (band weights
+ * included), so each plane is a float4 frame that wo_assemble_rows_device[_ex], a gather
+ * over ranks and wo_srgb8_encode_device take unchanged.  Asynchronous on `stream`, on the
+ * renderer's device, after an edited scene is compiled and uploaded, as the ray queries.
+ * The kernel is the ray queries' (wo_renderer_set_ray_tracer; wo_renderer_ray_path and
+ * wo_renderer_lanes_info report it); the specialised kernel is not used.
+ * -1 with wo_renderer_last_error, checked in this order before the device is touched:
+ * params == NULL; width, height or spp == 0; mode != WO_SHADING_PATHTRACE; nranks == 0,
+ * rank >= nranks or tile_rows == 0; a short plane_stride; a NULL or misaligned buffer;
+ * then a device-less renderer. */
+int wo_renderer_render_features_device(Wo_Renderer* r, Wo_RenderParams const* params, void* d_out, size_t plane_stride,
+                                       uint32_t tile_rows, uint32_t rank, uint32_t nranks, void* stream);
+/* The whole frame on one rank into HOST memory: 3 * width * height 16-byte rows, the
+ * planes contiguous (plane_stride = width * height), `out` 16-byte aligned.
+ * Synchronous; includes the copy.  Uses the renderer's device only, whatever
+ * wo_renderer_set_devices says. */
+int wo_renderer_render_features(Wo_Renderer* r, Wo_RenderParams const* params, void* out);
+
 /* Path-tracer kernel selection (results are identical; only speed differs).
  *   AUTO         union-only scenes of more than WOLOLO_LANES_MIN_PRIMS (256)
  *                primitives -> LANES; else scenes of up to WOLOLO_JIT_MAX_PRIMS
@@ -515,7 +594,8 @@ void wo_renderer_clear_error(void);
 /* sizeof(type) (field NULL) or offsetof(type, field) as this library was
  * compiled, for the value types of the C ABI (Wo_Vec3, Wo_Quaternion,
  * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame, Wo_Ray, Wo_RayHit,
- * Wo_RayCrossing, Wo_RaySpans, Wo_MassGrid, Wo_MassPlan, Wo_MassSums, Wo_MassProperties);
+ * Wo_RayCrossing, Wo_RaySpans, Wo_MassGrid, Wo_MassPlan, Wo_MassSums, Wo_MassProperties,
+ * Wo_FeatureIds);
  * (size_t)-1 for an unknown name.  Bindings check their mirrors with it. */
 size_t wo_abi_layout(char const* type, char const* field);
 /* Device self-check of the path tracer's fast correctly rounded square root
