@@ -115,8 +115,11 @@ typedef struct Gen {
     uint32_t nterm, term_bit0;
     struct TEnt *tgroups, *tterms;
     /* the sky-ray predicate is being written (gen_sky_rays): a lane's own tests, so no
-     * wave-level member skip (a met interval only narrows: the same emptiness) */
+     * wave-level member skip (a met interval only narrows: the same emptiness); 2 at the
+     * levels that test a literal by one member alone (gen_sky_term), `sky_only` then
+     * naming the member gen_members writes (kSkyAll: every member) */
     int sky;
+    uint32_t sky_only;
     int err;
 } Gen;
 
@@ -143,6 +146,8 @@ static int bound_tested(const Gen* g, uint32_t pc) {
     return 1;
 }
 
+enum { kSkyAll = 0xffffffffu }; /* Gen.sky_only: no member singled out */
+
 /* ---- collect: intersect every primitive of [start, end), fill the window ---- */
 static void gen_lone_sphere(Gen* g, const WoRec* L, uint32_t ord, int indent);
 
@@ -156,6 +161,7 @@ static void gen_members(Gen* g, uint32_t pc, uint32_t cnt, int indent) {
         const WoRec* L = &g->prog[pc + 1 + m];
         uint32_t vl[4];
         for (int i = 0; i < 4; ++i) vl[i] = fbits(L->f[i]);
+        if (g->sky_only != kSkyAll && m != g->sky_only) continue;
         if (m > 0 && !g->sky) /* empty on every lane: the other members cannot widen it */
             bput(g->b, "%*s  if (__ballot(!(iv.a > iv.b)) != 0ull) {\n", indent, ""), ++open_skips;
         bput(g->b, "%*s  {\n", indent, "");
@@ -168,7 +174,7 @@ static void gen_members(Gen* g, uint32_t pc, uint32_t cnt, int indent) {
             const int pos = L->f[L->u1 - 1u] > 0.0f; /* s1 = +1 */
             uint32_t vh[2] = {vl[3], fbits(L2->f[3])};
             bput(g->b, "%*s    WO_WK_N(WO_WORK_HALFSPACE_TESTS, 2u);\n", indent, "");
-            if (m == 0) bput(g->b, "%*s    wodev::ivl_open(iv);\n", indent, "");
+            if (m == 0 || m == g->sky_only) bput(g->b, "%*s    wodev::ivl_open(iv);\n", indent, "");
             /* dist1 = h1 - s1*oa, dist2 = h2 + s1*oa with h as a literal operand */
             bput(g->b,
                  "%*s    float dist1, dist2;\n"
@@ -893,12 +899,49 @@ static void gen_term_body(Gen* g, const SPrim* q, int indent) {
  * where it scatters (wo_device_common.h TracerSkyRays).
  * Level 1 tests the hierarchy's top groups; level 2 replaces a top group that has
  * child groups by those (a lone term under it by its own test).  (Every group opened
- * down to the terms accepts 69 % of csg32's scattered rays against 38 %, but its 13
- * term tests spill 72 B a lane to scratch: 2.79 ms against 2.37)  A term without such a
- * test (its first literal complemented) keeps the group above it, and the predicate is
- * left out where that is the root. */
+ * down to the terms with each term's whole first literal -- square roots, the slab's six
+ * faces -- spilled 72 B a lane to scratch: 2.79 ms against 2.37)  A term
+ * without such a test (its first literal complemented) keeps the group above it, and the
+ * predicate is left out where that is the root.
+ * Level 3 opens every group down to its terms and tests each term's first literal by
+ * one member alone: a convex primitive's interval is the meet of its members', and a
+ * met interval only narrows, so where one member's interval is empty or does not reach
+ * past t_min the literal's is neither.  The member is the primitive's smallest sphere
+ * -- the lane's side of sphere_need, which leaves the trace's interval of that sphere
+ * empty or ending behind the origin -- or else the face pair of the box's thinnest axis
+ * (csg32's slab: 0.5 against 12 x 12), written by gen_members with the same reach
+ * condition.  One reciprocal instead of three and no square root: 14 short tests, which
+ * the kernel holds in the registers it had (58 VGPRs, no scratch). */
 
-#define JIT_SKY_LEVELS 2
+#define JIT_SKY_LEVELS 3
+/* the smallest sphere among the members of the convex primitive at pc, or kSkyAll */
+static uint32_t sky_sphere_member(const Gen* g, uint32_t pc) {
+    uint32_t best = kSkyAll;
+    for (uint32_t m = 0; m < g->prog[pc].u0; ++m) {
+        const WoRec* L = &g->prog[pc + 1u + m];
+        if (L->op != WO_LEAF_SPHERE) continue;
+        if (best == kSkyAll || L->f[3] < g->prog[pc + 1u + best].f[3]) best = m; /* f[3] = r^2 */
+    }
+    return best;
+}
+
+/* the first member of the face pair (as gen_members fuses them: neighbours on one axis,
+ * opposite signs) with the least distance between its planes, or kSkyAll */
+static uint32_t sky_thin_pair(const Gen* g, uint32_t pc) {
+    uint32_t best = kSkyAll;
+    float thin = 0.0f;
+    for (uint32_t m = 0; m + 1u < g->prog[pc].u0; ++m) {
+        const WoRec *L = &g->prog[pc + 1u + m], *L2 = L + 1;
+        if (!(L->op == WO_LEAF_HALFSPACE && L->u1 != 0u && L2->op == WO_LEAF_HALFSPACE && L2->u1 == L->u1 &&
+              (L->f[L->u1 - 1u] > 0.0f) != (L2->f[L2->u1 - 1u] > 0.0f)))
+            continue;
+        const float extent = L->f[3] + L2->f[3]; /* s x <= h1 and -s x <= h2: -h2 <= s x <= h1 */
+        if (best == kSkyAll || extent < thin) best = m, thin = extent;
+        ++m;
+    }
+    return best;
+}
+
 /* a term's test: `gone = gone & <the term cannot be met>`; 0 when it has none */
 static int gen_sky_term(Gen* g, const SPrim* q, int indent) {
     if (!q->term || !q->npc) return 0;
@@ -908,13 +951,18 @@ static int gen_sky_term(Gen* g, const SPrim* q, int indent) {
     if (!pos0) return 0;
     const WoRec* P = &g->prog[pc0];
     bput(g->b, "%*s{  // a term on its own: primitive %u\n", indent, "", P->u1);
-    if (q->npc == 1u && P->u0 == 1u && g->prog[pc0 + 1u].op == WO_LEAF_SPHERE) {
-        put_lone_disc(g, &g->prog[pc0 + 1u], indent);
+    /* the sphere tested alone: a lone sphere's, at level 3 the smallest of any first literal */
+    uint32_t ms = q->npc == 1u && P->u0 == 1u && g->prog[pc0 + 1u].op == WO_LEAF_SPHERE ? 0u : kSkyAll;
+    if (g->sky == 2) ms = sky_sphere_member(g, pc0);
+    if (ms != kSkyAll) {
+        put_lone_disc(g, &g->prog[pc0 + 1u + ms], indent);
         bput(g->b, "%*s  gone = gone & !wodev::sphere_need(b, disc);\n%*s}\n", indent, "", indent, "");
         return 1;
     }
+    if (g->sky == 2) g->sky_only = sky_thin_pair(g, pc0); /* kSkyAll where it has none: every member */
     bput(g->b, "%*s  wodev::Ivl ia;\n", indent, "");
     gen_term_ivl(g, pc0, "ia", indent + 2);
+    g->sky_only = kSkyAll;
     bput(g->b, "%*s  gone = gone & !(" JIT_TERM_REACH ");\n%*s}\n", indent, "", indent, "");
     return 1;
 }
@@ -923,7 +971,8 @@ static int gen_sky_term(Gen* g, const SPrim* q, int indent) {
 static int gen_sky_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root, int level) {
     if (n == 0u) return 1;
     if (n == 1u) return gen_sky_term(g, &p[0], indent);
-    if (root || (level > 1 && n > g->spatial_leaf)) {
+    const int all = level >= 3; /* every group opened, the leaf groups to their terms */
+    if (root || all || (level > 1 && n > g->spatial_leaf)) {
         /* the children instead, into a buffer of their own: kept only when each has a test */
         Buf sub = {0};
         Buf* keep = g->b;
@@ -933,7 +982,7 @@ static int gen_sky_spatial(Gen* g, SPrim* p, uint32_t n, int indent, int root, i
             for (uint32_t i = 0; i < n && ok; ++i) ok = gen_sky_term(g, &p[i], indent);
         } else {
             const uint32_t cut = spatial_cut(p, n);
-            const int below = root ? level : level - 1;
+            const int below = root || all ? level : level - 1;
             ok = gen_sky_spatial(g, p, cut, indent, 0, below) && gen_sky_spatial(g, p + cut, n - cut, indent, 0, below);
         }
         g->b = keep;
@@ -963,7 +1012,7 @@ static int gen_sky_rays(Gen* g, int level) {
     Buf body = {0};
     Buf* keep = g->b;
     g->b = &body;
-    g->sky = 1;
+    g->sky = level >= 3 ? 2 : 1;
     int ok = 1;
     for (uint32_t i = 0; i < g->ntunb && ok; ++i) ok = gen_sky_term(g, &g->tunb[i], 4);
     ok = ok && gen_sky_spatial(g, p, g->nsprims, 4, 1, level);
@@ -2267,6 +2316,7 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
     g.prog = prog;
     g.n = n_recs;
     g.b = &b;
+    g.sky_only = kSkyAll;
     uint32_t nw = n_prims ? (n_prims + 31u) / 32u : 1u;
     /* Wave-level BOUND tests pay only for larger subtrees (csg32 5.17 ms testing
      * subtrees of >= 8 leaves vs 6.94 testing every BOUND; later 4.93 at >= 6, 4.95
@@ -2647,9 +2697,14 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
         if (L == 0) have_sky = ok;
         if (!ok) break;
     }
-    /* level 2 by default (csg32, 1920x1080x64: 2.428 ms without the predicate, 2.413 at
-     * level 1, 2.369 at level 2; profiles/sky_rays_ab.txt) */
-    if (have_sky) bput(&b, "#ifndef WO_SKY_RAYS\n#define WO_SKY_RAYS 2  // 0: no sky-ray predicate; 1, 2: its level\n#endif\n");
+    /* the sharpest level the scene has by default (csg32, 1920x1080x64: 2.428 ms without
+     * the predicate, 2.413 at level 1, 2.369 at level 2, profiles/sky_rays_ab.txt; later
+     * 2.249 at level 2 against 2.139 at level 3, profiles/sky_rays_terms_ab.txt) */
+    int sky_default = 0;
+    while (sky_default < JIT_SKY_LEVELS && sky[sky_default].s) ++sky_default;
+    if (have_sky)
+        bput(&b, "#ifndef WO_SKY_RAYS\n#define WO_SKY_RAYS %d  // 0: no sky-ray predicate; 1 to %d: its level\n#endif\n",
+             sky_default, sky_default);
     bput(&b, "struct JitTracer {\n");
     if (n_tile) {
         bput(&b,

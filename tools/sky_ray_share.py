@@ -26,6 +26,12 @@ flag sets against each other, e.g. the thresholds of WO_SKY_RAYS_BOUNCE_MIN.
 
     python tools/sky_ray_share.py --take-probe --flags=-DWO_SKY_RAYS_BOUNCE_MIN=1 --out profiles/sky_rays_take_before.txt
     python tools/sky_ray_share.py --ab 4 --variants "all=-DWO_SKY_RAYS_BOUNCE_MIN=1;cam=-DWO_SKY_RAYS_BOUNCE_MIN=65"
+
+--terms-probe compares levels on the same rays: each level's predicate runs in every iteration
+with a lane that goes on and ends no path (probes 10..13), counted apart for camera and bounce
+iterations; and it counts the bounce iterations that run once the tile's jobs are drained.
+
+    python tools/sky_ray_share.py --terms-probe --levels 2,3 --out profiles/sky_rays_terms_before.txt
 """
 import argparse
 import os
@@ -66,7 +72,10 @@ def main():
     ap.add_argument("--ab", type=int, default=0, help="alternating rounds timing the levels (0 included as listed)")
     ap.add_argument("--take-probe", action="store_true",
                     help="the predicate block's executions and lanes, the bounce and camera iterations (with --flags)")
-    ap.add_argument("--flags", default="", help="--take-probe: the build's WOLOLO_JIT_FLAGS")
+    ap.add_argument("--terms-probe", action="store_true",
+                    help="per level, the rays tested and accepted in camera and in bounce iterations with no path "
+                         "ended, and the drained bounce iterations (with --flags)")
+    ap.add_argument("--flags", default="", help="--take-probe, --terms-probe: the build's WOLOLO_JIT_FLAGS")
     ap.add_argument("--variants", default=None, help="time named flag sets: 'name=flags;name=flags' (rounds: --ab)")
     ap.add_argument("--cpu", action="store_true", help="the oracle's share too")
     ap.add_argument("--cpu-rays", type=int, default=20000, help="--cpu: camera rays")
@@ -139,6 +148,34 @@ def main():
                 f"iterations ({per(n[5], n[3])} a block); {per(n[4] + n[5], n[2] + n[3])} a block overall")
             say(f"(c) bounce iterations that trace: {n[6]}, busy lanes {n[7]} ({per(n[7], n[6])} a trace)")
             say(f"(d) camera iterations: {n[8]}, jobs {n[9]} ({per(n[9], n[8])} an iteration)")
+        elif a.terms_probe:
+            # per level: the predicate emitted in every iteration with a lane that goes on
+            # (WO_SKY_RAYS_BOUNCE_MIN=1) and ending no path (probes 10..13), so every level
+            # sees the same rays; then the drain's part of the bounce iterations (6, 7, 14, 15)
+            r, p = renderer("-DWO_SKY_RAYS=0")
+            S, P = segments(r, p), p.width * p.height * p.spp
+            r.close()
+            say(f"{a.scene} {p.width}x{p.height} {p.spp} spp depth {p.max_depth}: {S} segments, {P} primary")
+
+            def count(flags, kind):
+                r, p = renderer(f"{flags} -DWO_SKY_RAYS_PROBE={kind}")
+                n = segments(r, p) - S
+                r.close()
+                return n
+
+            share = {}
+            for L in levels:
+                f = f"-DWO_SKY_RAYS={L} -DWO_SKY_RAYS_BOUNCE_MIN=1"
+                ca, ba, ct, bt = (count(f, k) for k in (10, 11, 12, 13))
+                share[L] = ca / ct
+                say(f"level {L}, ending none: camera iterations {ct} rays tested, {ca} accepted ({100.0 * ca / ct:.2f} %); "
+                    f"bounce iterations {bt} continuing rays tested, {ba} accepted ({100.0 * ba / bt:.2f} %)")
+            if len(levels) > 1:
+                say(f"camera share, level {levels[-1]} / level {levels[0]}: {share[levels[-1]] / share[levels[0]]:.3f}")
+            n = {k: count(a.flags, k) for k in (6, 7, 14, 15)}
+            say(f"flags '{a.flags}': bounce iterations that trace {n[6]}, busy lanes {n[7]} ({n[7] / n[6]:.2f} a trace); of them "
+                f"with the tile's jobs drained {n[14]}, busy lanes {n[15]} ({n[15] / max(n[14], 1):.2f} a trace); before the "
+                f"drain {n[6] - n[14]}, busy lanes {n[7] - n[15]} ({(n[7] - n[15]) / max(n[6] - n[14], 1):.2f} a trace)")
         elif a.variants:
             # named flag sets against each other, as --ab does for the levels
             vs = [v.split("=", 1) for v in a.variants.split(";") if v]
