@@ -55,6 +55,8 @@ static const AbiField kAbi[] = {
     F(Wo_MassProperties, crossings),
     T(Wo_FeatureIds), F(Wo_FeatureIds, node), F(Wo_FeatureIds, leaf), F(Wo_FeatureIds, material),
     F(Wo_FeatureIds, flags),
+    T(Wo_DenoiseParams), F(Wo_DenoiseParams, levels), F(Wo_DenoiseParams, flags), F(Wo_DenoiseParams, k_color),
+    F(Wo_DenoiseParams, k_normal), F(Wo_DenoiseParams, k_depth), F(Wo_DenoiseParams, reserved),
 };
 
 #undef T

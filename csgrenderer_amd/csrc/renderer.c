@@ -17,6 +17,7 @@
 #include <string.h>
 #include <time.h>
 
+#include "wo_denoise.h"
 #include "wo_internal.h"
 
 static _Thread_local char g_err[512];
@@ -1268,6 +1269,80 @@ int wo_srgb8_encode_device(void const* d_rgba, void* d_bgra8, size_t pixels, voi
         return -1;
     }
     return 0;
+}
+
+/* ---------------------------------------------------------------- denoiser */
+
+int wo_denoise_device(Wo_DenoiseParams const* dp, uint32_t width, uint32_t height, void const* d_color,
+                      void const* d_albedo, void const* d_normal, void const* d_ids, void* d_out, void* d_scratch,
+                      size_t scratch_bytes, void* stream) {
+    static char const what[] = "denoise_device";
+    if (wo_denoise_check_params(what, dp)) return -1;
+    if (wo_denoise_check_extent(what, width, height)) return -1;
+    if (wo_denoise_check_planes(what, dp, width, height, d_color, d_albedo, d_normal, d_ids, d_out, d_scratch,
+                                scratch_bytes, 1))
+        return -1;
+    char err[256] = {0};
+    if (wo_dev_denoise(dp, width, height, d_color, d_albedo, d_normal, d_ids, d_out, d_scratch, stream, err, sizeof err)) {
+        wo_set_error("%s: %s", what, err);
+        return -1;
+    }
+    return 0;
+}
+
+/* The frame (16-row tiles, one rank: wo_renderer_render_f32's), its planes (one band of the frame's
+ * height: wo_renderer_render_features') and the filter, in order on the device's default stream. */
+int wo_renderer_render_denoised(Wo_Renderer* r, Wo_RenderParams const* params, Wo_DenoiseParams const* dp_or_null,
+                                float* out_rgba) {
+    static char const what[] = "render_denoised";
+    if (!r) return -1;
+    if (!params || !out_rgba) {
+        wo_set_error("%s: NULL %s", what, !params ? "params" : "out_rgba");
+        return -1;
+    }
+    Wo_DenoiseParams dp;
+    if (dp_or_null)
+        dp = *dp_or_null;
+    else
+        wo_denoise_params_default(&dp);
+    if (wo_denoise_check_params(what, &dp)) return -1;
+    if (wo_denoise_check_extent(what, params->width, params->height)) return -1;
+    if (params->spp == 0u) {
+        wo_set_error("%s: spp must not be 0", what);
+        return -1;
+    }
+    if (params->mode != (uint32_t)WO_SHADING_PATHTRACE) {
+        wo_set_error("%s: mode %u is not WO_SHADING_PATHTRACE", what, params->mode);
+        return -1;
+    }
+    if (!r->dev) {
+        wo_set_error("%s: the renderer has no HIP device (created with WOLOLO_ALLOW_NO_DEVICE)", what);
+        return -1;
+    }
+    if (sync_device(r)) return -1;
+    const uint32_t W = params->width, H = params->height;
+    const size_t pixels = (size_t)W * H, scratch_bytes = wo_denoise_scratch_bytes(W, H, &dp);
+    char err[256] = {0};
+    const int cur = wo_dev_current();
+    WoDenoiseWork work;
+    int rc = wo_dev_denoise_work_begin(r->device, (size_t)wo_rank_local_rows(H, 16u, 1u) * W, pixels, scratch_bytes, &work,
+                                       err, sizeof err);
+    if (rc) wo_set_error("%s: %s", what, err);
+    char* planes = (char*)work.d_planes;
+    if (!rc) rc = wo_renderer_render_rows_device(r, params, work.d_color, 16u, 0u, 1u, NULL, NULL);
+    if (!rc) rc = wo_renderer_render_features_device(r, params, planes, pixels, H, 0u, 1u, NULL);
+    if (!rc)
+        rc = wo_denoise_device(&dp, W, H, work.d_color, planes + WO_FEATURE_ALBEDO * pixels * 16u,
+                               planes + WO_FEATURE_NORMAL * pixels * 16u, planes + WO_FEATURE_IDS * pixels * 16u,
+                               work.d_out, work.d_scratch, scratch_bytes, NULL);
+    if (!rc) {
+        rc = wo_dev_denoise_work_finish(&work, out_rgba, pixels * 16u, err, sizeof err);
+        if (rc) wo_set_error("%s: %s", what, err);
+    } else {
+        wo_dev_denoise_work_free(&work);
+    }
+    if (cur >= 0) (void)wo_dev_select(cur);
+    return rc ? -1 : 0;
 }
 
 int wo_renderer_render_accumulate(Wo_Renderer* r, Wo_RenderParams const* params, float* out_rgba, int reset) {

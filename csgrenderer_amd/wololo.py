@@ -150,6 +150,16 @@ FEATURE_IDS_FIELDS = [("node", "<u4"), ("leaf", "<u4"), ("material", "<u4"), ("f
 FEATURE_ALBEDO, FEATURE_NORMAL, FEATURE_IDS, FEATURE_PLANES = 0, 1, 2, 3
 assert ctypes.sizeof(FeatureIds) == 16
 
+
+# renderer_ext.h Wo_DenoiseParams (the a-trous denoiser guided by the feature planes)
+class DenoiseParams(Structure):
+    _fields_ = [("levels", c_uint32), ("flags", c_uint32), ("k_color", c_float), ("k_normal", c_float),
+                ("k_depth", c_float), ("reserved", c_uint32)]
+
+
+DENOISE_DEMODULATE, DENOISE_STOP_AT_NODES, DENOISE_MAX_LEVELS = 1, 2, 8
+assert ctypes.sizeof(DenoiseParams) == 24
+
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 32
 assert ctypes.sizeof(RayCrossing) == 16 and ctypes.sizeof(RaySpans) == 16
 assert ctypes.sizeof(Vec3) == 24 and ctypes.sizeof(Quaternion) == 32 and ctypes.sizeof(NodeArgument) == 64
@@ -238,6 +248,13 @@ SIGNATURES = {
     "wo_renderer_render_features_device": (c_int, [c_void_p, POINTER(RenderParams), c_void_p, c_size_t, c_uint32,
                                                    c_uint32, c_uint32, c_void_p]),
     "wo_renderer_render_features": (c_int, [c_void_p, POINTER(RenderParams), c_void_p]),
+    "wo_denoise_params_default": (None, [POINTER(DenoiseParams)]),
+    "wo_denoise_scratch_bytes": (c_size_t, [c_uint32, c_uint32, POINTER(DenoiseParams)]),
+    "wo_denoise_device": (c_int, [POINTER(DenoiseParams), c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wo_denoise_host": (c_int, [POINTER(DenoiseParams), c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "wo_renderer_render_denoised": (c_int, [c_void_p, POINTER(RenderParams), POINTER(DenoiseParams), c_void_p]),
     "wo_renderer_set_jit_async": (None, [c_void_p, c_int]),
     "wo_renderer_jit_pending": (c_int, [c_void_p]),
     "wo_renderer_prepare": (c_int, [c_void_p]),
@@ -599,6 +616,16 @@ class Renderer:
                                                        nranks, c_void_p(stream or None)):
             raise WololoError(last_error())
 
+    def render_denoised(self, params: RenderParams, dp: "DenoiseParams | None" = None):
+        """The denoised PATHTRACE frame of `params` ((H, W, 4) float32): the frame, its feature planes
+        and wo_denoise_device on the renderer's device, then one copy.  dp None = the defaults."""
+        import numpy as np
+        out = np.zeros((int(params.height), int(params.width), 4), dtype=np.float32)
+        if self.lib.wo_renderer_render_denoised(self.ptr, ctypes.byref(params), ctypes.byref(dp) if dp is not None else None,
+                                                out.ctypes.data_as(c_void_p)):
+            raise WololoError(last_error())
+        return out
+
     def frame_desc(self, params: RenderParams, tile_rows=16, rank=0, nranks=1) -> WoFrame:
         fr = WoFrame()
         if self.lib.wo_renderer_frame_desc(self.ptr, ctypes.byref(params), tile_rows, rank, nranks,
@@ -760,6 +787,50 @@ def srgb8_encode_host(rgba):
 
 def srgb8_encode_device(d_rgba: int, d_bgra8: int, pixels: int, stream: int = 0):
     if load().wo_srgb8_encode_device(c_void_p(d_rgba), c_void_p(d_bgra8), pixels, c_void_p(stream or None)):
+        raise WololoError(last_error())
+
+
+def denoise_params(levels=None, flags=None, k_color=None, k_normal=None, k_depth=None) -> DenoiseParams:
+    """wo_denoise_params_default with the given fields replaced."""
+    dp = DenoiseParams()
+    load().wo_denoise_params_default(ctypes.byref(dp))
+    for name, v in (("levels", levels), ("flags", flags), ("k_color", k_color), ("k_normal", k_normal),
+                    ("k_depth", k_depth)):
+        if v is not None:
+            setattr(dp, name, v)
+    return dp
+
+
+def denoise_scratch_bytes(width: int, height: int, dp: DenoiseParams) -> int:
+    """Bytes of device scratch wo_denoise_device needs; raises on bad arguments (the C call returns 0)."""
+    n = int(load().wo_denoise_scratch_bytes(width, height, ctypes.byref(dp) if dp is not None else None))
+    if n == 0:
+        raise WololoError(last_error())
+    return n
+
+
+def denoise_host(dp: DenoiseParams, color, albedo=None, normal=None, ids=None):
+    """wo_denoise_host on numpy planes: color, albedo, normal (H, W, 4) float32, ids (H, W) of
+    FEATURE_IDS_FIELDS (or (H, W, 4) uint32); the optional ones may be None.  Returns (H, W, 4) float32."""
+    import numpy as np
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    h, w = color.shape[:2]
+    planes = [None if a is None else np.ascontiguousarray(a) for a in (albedo, normal, ids)]
+    out = np.zeros((h, w, 4), dtype=np.float32)
+    ptr = [c_void_p(a.ctypes.data) if a is not None else None for a in planes]
+    if load().wo_denoise_host(ctypes.byref(dp), w, h, c_void_p(color.ctypes.data), ptr[0], ptr[1], ptr[2],
+                              c_void_p(out.ctypes.data)):
+        raise WololoError(last_error())
+    return out
+
+
+def denoise_device(dp: DenoiseParams, width: int, height: int, d_color: int, d_albedo: int, d_normal: int, d_ids: int,
+                   d_out: int, d_scratch: int, scratch_bytes: int, stream: int = 0):
+    """wo_denoise_device on device addresses (0 = NULL), asynchronously on `stream`."""
+    if load().wo_denoise_device(ctypes.byref(dp) if dp is not None else None, width, height, c_void_p(d_color or None),
+                                c_void_p(d_albedo or None), c_void_p(d_normal or None), c_void_p(d_ids or None),
+                                c_void_p(d_out or None), c_void_p(d_scratch or None), int(scratch_bytes),
+                                c_void_p(stream or None)):
         raise WololoError(last_error())
 
 

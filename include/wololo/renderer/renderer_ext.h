@@ -499,6 +499,90 @@ int wo_renderer_render_features_device(Wo_Renderer* r, Wo_RenderParams const* pa
  * wo_renderer_set_devices says. */
 int wo_renderer_render_features(Wo_Renderer* r, Wo_RenderParams const* params, void* out);
 
+/* ---- edge-avoiding a-trous denoiser guided by the feature buffers ----
+ * The consumer of the planes above: `levels` passes of a 5x5 B3-spline stencil whose taps
+ * are 2^i pixels apart in pass i, each tap weighted down by how far its colour, normal and
+ * depth are from the centre's.  No transcendental function: every operation below is fp32
+ * and rounded once, nothing is contracted, and 1.0f / x is the correctly rounded reciprocal,
+ * so the device form, the host form and a CPU restatement agree bit for bit.
+ *
+ * Planes: width * height 16-byte rows each, row 0 at the top, 16-byte aligned.  `color` is a
+ * frame as wo_renderer_render_rows_device (assembled) or wo_renderer_render_frame_device
+ * leaves it; `albedo` and `normal` are planes WO_FEATURE_ALBEDO and WO_FEATURE_NORMAL (the
+ * normal plane's w is the depth, +INFINITY where nothing was hit); `ids` is plane
+ * WO_FEATURE_IDS.  albedo may be NULL only without WO_DENOISE_DEMODULATE, normal only when
+ * k_normal == 0 && k_depth == 0, ids only without WO_DENOISE_STOP_AT_NODES.
+ *
+ *   clampf(v, lo, hi):  t = v > lo ? v : lo;  t < hi ? t : hi           (a NaN becomes lo)
+ *   E(d2, k):           x = 1.0f - d2 * k;  m = x > 0 ? x : 0;  m * m   (a NaN gives 0)
+ *   |d|^2:              (d.x d.x + d.y d.y) + d.z d.z
+ * Demodulation (WO_DENOISE_DEMODULATE; per pixel and channel i): a'_i = clampf(albedo_i,
+ * 0x1p-7f, 0x1p20f) and c_i = color_i * (1.0f / a'_i); otherwise c = color.rgb.
+ * Depth (per pixel): z = normal.w; fin = z < INFINITY (false for a NaN); rz = 1.0f /
+ * clampf(z, 0x1p-20f, 0x1p20f).
+ * Pass i = 0 .. levels-1 reads the image c and writes c', with s = 1 << i and kc = k_color *
+ * (float)(1u << 2i).  For the centre p = (x, y): sum = (0, 0, 0), wsum = 0; then dy = -2..2
+ * (outer) and dx = -2..2 (inner), the tap q = (x + dx s, y + dy s) in signed arithmetic; a q
+ * outside the frame is skipped.  h = H[|dx|] * H[|dy|], H = {0.375f, 0.25f, 0.0625f}.  The
+ * centre tap has w = h.  Any other tap starts with e = 1.0f and applies the enabled terms in
+ * this order:
+ *   k_color > 0:   e *= E(|c_q - c_p|^2, kc);
+ *   k_normal > 0:  e *= E(|n_q - n_p|^2, k_normal), n = normal.xyz as stored;
+ *   k_depth > 0:   both fin: rel = (z_q - z_p) * rz_p, e *= E(rel * rel, k_depth);
+ *                  neither fin: e unchanged;  exactly one fin: e = 0;
+ *   WO_DENOISE_STOP_AT_NODES: ids_q.node != ids_p.node sets e = 0;
+ * and w = h * e.  A tap with !(w > 0) is skipped entirely (a non-finite neighbour that a term
+ * rejects never reaches the sum); otherwise sum_i += w * c_q,i (a product, then a sum) and
+ * wsum += w.  c'_p = sum * (1.0f / wsum); the centre tap alone gives wsum >= 9/64.
+ * After the last pass out.rgb = c * a' with WO_DENOISE_DEMODULATE, else c; out.w is color.w,
+ * copied bit for bit.  Every reciprocal's argument lies in [2^-20, 2^20]. */
+#define WO_DENOISE_DEMODULATE    1u  /* divide by the first-hit albedo before filtering, multiply after */
+#define WO_DENOISE_STOP_AT_NODES 2u  /* a tap whose Wo_FeatureIds.node differs from the centre's gets weight 0 */
+#define WO_DENOISE_MAX_LEVELS    8u
+typedef struct Wo_DenoiseParams {   /* 24 bytes */
+    uint32_t levels;                /* 1 .. 8 a-trous iterations; iteration i uses step 2^i */
+    uint32_t flags;                 /* WO_DENOISE_* ; other bits rejected */
+    float k_color, k_normal, k_depth; /* finite, >= 0; 0 switches the term off */
+    uint32_t reserved;              /* 0 */
+} Wo_DenoiseParams;
+#define WO_DENOISE_MAX_EXTENT 32768u
+/* 5 levels, WO_DENOISE_DEMODULATE, k_color 0.25f, k_normal 4.0f, k_depth 100.0f. */
+void wo_denoise_params_default(Wo_DenoiseParams* dp);
+/* Bytes of device scratch wo_denoise_device needs for a width x height frame: the ping-pong
+ * working images, width * height * 16 bytes for one level and twice that for more.  0 on bad
+ * arguments (wo_renderer_last_error names the first). */
+size_t wo_denoise_scratch_bytes(uint32_t width, uint32_t height, Wo_DenoiseParams const* dp);
+/* The filter on DEVICE memory: library-level, like wo_srgb8_encode_device -- on the current HIP
+ * device, asynchronously on `stream` (NULL = the default stream).  Allocates nothing: d_scratch
+ * holds at least wo_denoise_scratch_bytes bytes (more is accepted; only that many are written).
+ * d_out and d_scratch must not overlap an input or each other.  A prologue kernel writes the
+ * (demodulated) working image, one kernel per level filters it, the last one into d_out.
+ * Per level the kernel either reads its taps from global memory or stages a workgroup's tile
+ * and halo in LDS; WOLOLO_DENOISE_FORM = lds | direct | auto (default) picks, `lds` falling
+ * back to `direct` at a step whose tile no longer fits.  The results do not depend on it.
+ * -1 with wo_renderer_last_error naming the argument, checked in this order before the device
+ * is touched: NULL params; levels outside 1 .. 8; unknown flag bits; reserved != 0; a negative
+ * or non-finite k_*; width or height 0 or above 32768; a required plane (color, out, scratch,
+ * and albedo / normal / ids as above) NULL; a misaligned pointer; out or scratch overlapping an
+ * input or each other; short scratch. */
+int wo_denoise_device(Wo_DenoiseParams const* dp, uint32_t width, uint32_t height, void const* d_color,
+                      void const* d_albedo, void const* d_normal, void const* d_ids, void* d_out, void* d_scratch,
+                      size_t scratch_bytes, void* stream);
+/* The same filter in host C on host memory, bit for bit; needs no device and no scratch.  The
+ * same checks in the same order. */
+int wo_denoise_host(Wo_DenoiseParams const* dp, uint32_t width, uint32_t height, void const* color,
+                    void const* albedo, void const* normal, void const* ids, void* out);
+/* A denoised frame into HOST memory (width * height * 4 floats): the WO_SHADING_PATHTRACE frame
+ * of `params` (params->mode must say so), that frame's feature planes, wo_denoise_device with
+ * `dp_or_null` (NULL = the defaults) and one copy to the host, in order on one stream of the
+ * renderer's own device (whatever wo_renderer_set_devices says, as render_features).
+ * Synchronous.  Bit for bit wo_denoise_host applied to wo_renderer_render_f32's and
+ * wo_renderer_render_features' outputs.  -1 for NULL params or out_rgba, bad denoise
+ * parameters (as above), a width, height or spp of 0, another mode; then for a device-less
+ * renderer. */
+int wo_renderer_render_denoised(Wo_Renderer* r, Wo_RenderParams const* params, Wo_DenoiseParams const* dp_or_null,
+                                float* out_rgba);
+
 /* Path-tracer kernel selection (results are identical; only speed differs).
  *   AUTO         union-only scenes of more than WOLOLO_LANES_MIN_PRIMS (256)
  *                primitives -> LANES; else scenes of up to WOLOLO_JIT_MAX_PRIMS
@@ -595,7 +679,7 @@ void wo_renderer_clear_error(void);
  * compiled, for the value types of the C ABI (Wo_Vec3, Wo_Quaternion,
  * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame, Wo_Ray, Wo_RayHit,
  * Wo_RayCrossing, Wo_RaySpans, Wo_MassGrid, Wo_MassPlan, Wo_MassSums, Wo_MassProperties,
- * Wo_FeatureIds);
+ * Wo_FeatureIds, Wo_DenoiseParams);
  * (size_t)-1 for an unknown name.  Bindings check their mirrors with it. */
 size_t wo_abi_layout(char const* type, char const* field);
 /* Device self-check of the path tracer's fast correctly rounded square root
