@@ -7,7 +7,7 @@
  * which costs ~1 s for csg32 and 10+ s for csg256 on every process and every
  * rank.  This file keeps the code objects on disk, keyed by the SHA-256 of
  * everything that determines them (source, embedded headers, target, compile
- * options, hiprtc version: the key is computed in trace_kernels.hip), so a
+ * options, hiprtc version: the key is computed in jit_code.cpp), so a
  * second process or rank loads the object instead of compiling it.
  *
  * Location: $WOLOLO_JIT_CACHE (a directory; "0" or "" disables the cache), else

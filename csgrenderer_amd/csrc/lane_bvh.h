@@ -1,5 +1,5 @@
 /*
- * lane_bvh.h -- what the lane tracer's kernels (trace_kernels.hip) and the host
+ * lane_bvh.h -- what the lane tracer's kernels (wo_tracers.h) and the host
  * builder of its ordered BVH (lane_bvh_build.cpp) share: the descriptor of a
  * built BVH, the encodings of its packed blob, and the size of the walk's LDS.
  * The blob's sections and their order: DESIGN.md §3.6f.

@@ -1,5 +1,5 @@
 // lane_bvh_build.cpp -- the host builder of the lane tracer's ordered BVH
-// (trace_kernels.hip, LaneTracer): from a compiled program to a descriptor and one
+// (wo_tracers.h, LaneTracer): from a compiled program to a descriptor and one
 // packed blob (lane_bvh.h).  Plain C++: no kernels, no runtime calls, no device.
 // The tree is over the primitives of a union-only program, over the terms of a
 // union of small conjunctions, else over the primitives of the general tree.

@@ -4,7 +4,7 @@
  * The reference presents through a swapchain whose format it picks as
  * B8G8R8A8_SRGB when available (renderer.c:813-832): the hardware clamps the
  * fragment output to [0, 1], applies the sRGB transfer function and quantises to
- * 8 bits.  Here the encode runs on the GPU (srgb8_kernel, trace_kernels.hip)
+ * 8 bits.  Here the encode runs on the GPU (srgb8_kernel, path_kernels.h)
  * into the same B8G8R8A8 layout; this file holds its table and the PPM dump.
  *
  * Exactness: an 8-bit code is a count of thresholds.  Threshold j (0..254) is

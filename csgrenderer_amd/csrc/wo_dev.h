@@ -1,6 +1,6 @@
 /*
  * wo_dev.h -- internal C ABI between the C host library (renderer.c) and the
- * HIP backend (trace_kernels.hip).  Replaces the reference's Vulkan backend
+ * HIP backend (trace_kernels.hip, query_launch.hip).  Replaces the reference's Vulkan backend
  * surface (renderer.c:394-1810 init, 2085-2219 per-frame dispatch).
  * Not installed; public entry points are in include/wololo/.
  */
@@ -60,7 +60,7 @@ WoJitJob* wo_jit_job_start(WoDev* dev, const char* src);
 int wo_jit_job_done(WoJitJob* job);
 const char* wo_jit_job_source(WoJitJob* job);
 int wo_jit_job_finish(WoJitJob* job, char* err, size_t errlen);
-/* Lane traversal kernel (union-only programs, see trace_kernels.hip). */
+/* Lane traversal kernel (union-only programs, see wo_tracers.h). */
 int wo_dev_lanes_available(WoDev* dev);
 void wo_dev_set_lanes(WoDev* dev, int on);
 double wo_dev_jit_compile_sec(WoDev* dev);

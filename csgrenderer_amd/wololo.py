@@ -431,7 +431,7 @@ class Renderer:
 
     def lanes_info(self):
         """The lane tracer's BVH: {"nodes", "depth", "top", "always", "kind"} ("kind": the kernel
-        form of the last path or ray launch, trace_kernels.hip PathKind), or None if not on the lane tracer."""
+        form of the last path or ray launch, wo_dev_impl.h PathKind), or None if not on the lane tracer."""
         out = (c_uint32 * 5)()
         if self.lib.wo_renderer_lanes_info(self.ptr, out) < 0:
             return None

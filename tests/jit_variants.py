@@ -1,7 +1,7 @@
 """The compile-time switches of the specialised kernel: a table and nothing else.
 
-One entry per `WO_*` macro that sits under `#ifndef` in wo_device_common.h, trace_kernels.hip
-or the text scene_jit.c emits, and one per environment knob that rewrites that text.  Classes:
+One entry per `WO_*` macro that sits under `#ifndef` in wo_device_common.h, the library
+kernels' headers (wo_tracers.h, path_kernels.h, query_kernels.h) or the text scene_jit.c emits, and one per environment knob that rewrites that text.  Classes:
 
   variant          set through WOLOLO_JIT_FLAGS (the two knobs: through the environment); changes
                    how a wave works and never the image.
@@ -9,7 +9,7 @@ or the text scene_jit.c emits, and one per environment knob that rewrites that t
                    differs from the default's (tests/test_jit_variants.py proves each one);
                    `frames`: the frames the GPU file renders each row at.
   instrumentation  changes what the counters mean; the counting launches alone set it.  No row.
-  library-build    read only by the static kernels of trace_kernels.hip: a second build of the
+  library-build    read only by the library's static kernels (wo_tracers.h ...): a second build of the
                    library, out of scope.  Listed so that the completeness test knows them.
 
 Scenes: a row of test_gen_scenes.CASES (48x36), a scene of csgrenderer_amd.scenes (64x36),
@@ -34,7 +34,7 @@ def _i(reason):
     return {"class": INSTRUMENTATION, "reason": reason}
 
 
-def _l(reason="read by the static kernels of trace_kernels.hip alone"):
+def _l(reason="read by the library's static kernels alone"):
     return {"class": LIBRARY_BUILD, "reason": reason}
 
 
@@ -120,7 +120,7 @@ TABLE = {
         "TERM2", "PRIO", "PRIO_LEAF", "PRIO_TERM", "FUSED_SPHERE", "GWIN", "TRIP_NODES", "TRIP_LEAVES", "MIN_WAVES",
         "BVH_MIN_WAVES", "TERMS_MIN_WAVES", "DYN_MIN_WAVES", "DYN_TERMS_MIN_WAVES", "GENERAL_MIN_WAVES")},
 }
-# WO_SHADE_PRIO is also what the library's own build of the static kernels reads (trace_kernels.hip
+# WO_SHADE_PRIO is also what the library's own build of the static kernels reads (wo_tracers.h
 # sets its default before the shared header): that use is library-build, the row above is the
 # specialised kernel's.
 ALSO_LIBRARY_BUILD = ("WO_SHADE_PRIO",)

@@ -46,7 +46,7 @@ def _render_rows(r, p, rows):
 
 
 def assemble_np(gathered, width, height, tile, n, band=(0, 0)):
-    """numpy statement of assemble_kernel (trace_kernels.hip): frame row y is row
+    """numpy statement of assemble_kernel (path_kernels.h): frame row y is row
     lb * tile + y mod tile of the rank whose local band lb is frame band y div tile."""
     from csgrenderer_amd import wololo as wl
     lr = wl.local_rows(height, tile, n, band)

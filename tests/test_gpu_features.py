@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 W, H = 67, 45  # no multiple of 8 or 64; 16-row tiles leave three local rows past the frame
 CASES = [(s, "interpreter") for s in ("csg32", "csg32_nested", "csg32_union", "rtiow_cover")] + \
     [(s, "lanes") for s in tgr.LANE_FORMS]
-FOOTPRINTS = ("8x8", "64x1")  # trace_kernels.hip feature_tile
+FOOTPRINTS = ("8x8", "64x1")  # query_launch.hip feature_tile
 
 
 @pytest.fixture(scope="module")

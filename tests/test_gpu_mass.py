@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 SCENES = ["csg32", "csg32_nested", "csg256_chain", "rtiow_cover"]
 FIELDS = ("lo", "hi", "rays", "rays_hit", "crossings")
-# the kernel's other forms (trace_kernels.hip mass_tile / mass_window / mass_reduce / mass_block_flush): the
+# the kernel's other forms (query_launch.hip mass_tile / mass_window / mass_reduce / mass_block_flush): the
 # same integers
 FORMS = [{"WOLOLO_MASS_TILE": "64x1"}, {"WOLOLO_MASS_FLUSH": "wave"}, {"WOLOLO_MASS_WINDOW": "8"},
          {"WOLOLO_MASS_REDUCE": "shfl"},

@@ -20,7 +20,7 @@ BOXES = {
     "rtiow_cover": ((-11.0, -0.5, -11.0), (11.0, 2.5, 11.0)),
 }
 SEEDS = {"csg32": 101, "csg32_union": 102, "csg32_nested": 103, "rtiow_cover": 104}
-LANE_FORMS = {"csg32_union": 2, "rtiow_cover": 3}  # trace_kernels.hip PathKind of the lane walk
+LANE_FORMS = {"csg32_union": 2, "rtiow_cover": 3}  # wo_dev_impl.h PathKind of the lane walk
 CASES = [(s, "interpreter") for s in BOXES] + [(s, "lanes") for s in LANE_FORMS]
 
 

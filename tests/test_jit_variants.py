@@ -16,7 +16,9 @@ from csgrenderer_amd import wololo as wl
 from test_gen_scenes import BY_NAME, CASES, frame_params, make
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csgrenderer_amd", "csrc")
-SOURCES = ("wo_device_common.h", "trace_kernels.hip", "scene_jit.c")
+# the library kernels' device headers and the two units that instantiate them: where a library `#ifndef WO_*` may sit
+LIBRARY = ("wo_tracers.h", "path_kernels.h", "query_kernels.h", "trace_kernels.hip", "query_launch.hip")
+SOURCES = ("wo_device_common.h",) + LIBRARY + ("scene_jit.c",)
 BEHIND = ((0.0, 4.5, 10.0), (0.0, 9.0, 20.0), (0, 1, 0), 45.0, 0.0, 10.0)  # test_gpu_sky_tiles' all-sky camera
 SIZES = {"61x35": (61, 35), "13x7": (13, 7), "rank1of3": (61, 35)}
 
@@ -161,7 +163,7 @@ def _guarded(text):
 
 
 def test_the_table_names_every_switch(hostonly, monkeypatch):
-    """Every `#ifndef WO_*` of the three sources and of the generated text of the named scenes
+    """Every `#ifndef WO_*` of the sources and of the generated text of the named scenes
     and of one row per form has an entry, and every entry's macro still exists."""
     found = set()
     for f in SOURCES:
@@ -173,8 +175,10 @@ def test_the_table_names_every_switch(hostonly, monkeypatch):
     macros = {m for m in jv.TABLE if m.startswith("WO_")}
     assert found - macros == set(), "switches without an entry in tests/jit_variants.py"
     assert macros - found == set(), "entries whose macro is gone"
-    with open(os.path.join(CSRC, "trace_kernels.hip")) as fh:
-        static = _guarded(fh.read())
+    static = set()
+    for f in LIBRARY:
+        with open(os.path.join(CSRC, f)) as fh:
+            static |= _guarded(fh.read())
     for m, e in jv.TABLE.items():
         assert e["class"] in (jv.VARIANT, jv.INSTRUMENTATION, jv.LIBRARY_BUILD), m
         if e["class"] == jv.LIBRARY_BUILD:

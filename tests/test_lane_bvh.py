@@ -16,7 +16,7 @@ K_LITNEG, K_NOLIT, K_TERM_REC_F4 = 0x80000000, 0xFFFFFFFF, 5
 K_GREF_BITS, K_GREF_MASK = 15, 0x7FFF
 INF = math.inf
 
-# scene -> the lane tracer's form (trace_kernels.hip PathKind)
+# scene -> the lane tracer's form (wo_dev_impl.h PathKind)
 FORMS = {"csg32_union": 2, "rtiow_cover": 3, "csg32": 6, "csg256_balanced": 6, "csg512_balanced": 14,
          "csg32_nested": 7}
 
