@@ -57,6 +57,15 @@ static const AbiField kAbi[] = {
     F(Wo_FeatureIds, flags),
     T(Wo_DenoiseParams), F(Wo_DenoiseParams, levels), F(Wo_DenoiseParams, flags), F(Wo_DenoiseParams, k_color),
     F(Wo_DenoiseParams, k_normal), F(Wo_DenoiseParams, k_depth), F(Wo_DenoiseParams, reserved),
+    T(Wo_MeshGrid), F(Wo_MeshGrid, lo), F(Wo_MeshGrid, hi), F(Wo_MeshGrid, n), F(Wo_MeshGrid, iters),
+    F(Wo_MeshGrid, flags), F(Wo_MeshGrid, reserved),
+    T(Wo_MeshVertex), F(Wo_MeshVertex, p), F(Wo_MeshVertex, cell),
+    T(Wo_MeshQuad), F(Wo_MeshQuad, v),
+    T(Wo_MeshQuadIds), F(Wo_MeshQuadIds, leaf), F(Wo_MeshQuadIds, node), F(Wo_MeshQuadIds, material),
+    F(Wo_MeshQuadIds, flags),
+    T(Wo_MeshCounts), F(Wo_MeshCounts, vertices), F(Wo_MeshCounts, quads), F(Wo_MeshCounts, cap_quads),
+    F(Wo_MeshCounts, flags),
+    T(Wo_Mesh), F(Wo_Mesh, vertices), F(Wo_Mesh, quads), F(Wo_Mesh, quad_ids), F(Wo_Mesh, counts),
 };
 
 #undef T

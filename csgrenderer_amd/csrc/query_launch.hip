@@ -1,6 +1,6 @@
 // query_launch.hip -- the queries' half of wo_dev.h's C ABI for gfx950 (MI355X, CDNA4, wave64):
-// ray queries, first-hit feature buffers, ray spans, mass sums and point classification.
-// Instantiates the kernels of query_kernels.h and launches them along one path: the scene
+// ray queries, first-hit feature buffers, ray spans, mass sums, point classification and the
+// surface mesh.  Instantiates the kernels of query_kernels.h and mesh_kernels.h and launches them along one path: the scene
 // check, the query's own argument checks, query_plan (which kernel form, how much LDS),
 // query_launch (occupancy, grid, launch, record).  The host forms share host_round_trip.
 // The queries do not restore the caller's current device.
@@ -15,6 +15,7 @@
 
 #include "wo_dev_impl.h"
 #include "query_kernels.h"
+#include "mesh_kernels.h"
 
 // ---- which kernel: the library's query kernel of a kind, for the pointer forms of the
 // occupancy and launch calls ----
@@ -421,4 +422,103 @@ extern "C" int wo_dev_classify_points_host(WoDev* dev, void const* points, void*
         dev, pbytes + obytes, {{const_cast<void*>(points), 0, pbytes}}, "hipMemcpy(points)",
         [&](char* io) { return wo_dev_classify_points(dev, io, io + pbytes, n, dev->stream, err, errlen); },
         {{out, pbytes, obytes}}, "point query", err, errlen);
+}
+
+// ---- surface mesh of the solid: seven launches in order on one stream; not a ray launch ----
+
+// WOLOLO_MESH_PASSES = 1 .. 5 (measurement, tools/mesh_bench.py): stop after the corner pass, the
+// count, the scan, the edges, the vertices; the mesh is then incomplete.
+static int mesh_passes() {
+    const char* v = getenv("WOLOLO_MESH_PASSES");
+    const int n = v && *v ? atoi(v) : 5;
+    return n >= 1 && n <= 5 ? n : 5;
+}
+
+extern "C" int wo_dev_mesh(WoDev* dev, WoMeshLaunch const* ml_in, void* d_vertices, void* d_quads, void* d_quad_ids,
+                           void* d_counts, void* d_scratch, void* stream_v, char* err, size_t errlen) {
+    if (scene_check(dev, err, errlen)) return -1;
+    if (use_device(dev, err, errlen)) return -1;
+    WoMeshLaunch ml = *ml_in;
+    const WoMeshLayout lay = wo_mesh_layout(ml.n);
+    char* scratch = reinterpret_cast<char*>(d_scratch);
+    MeshBufs mb;
+    mb.bits = reinterpret_cast<uint64_t*>(scratch + lay.bits_off);
+    mb.masks = reinterpret_cast<uint64_t*>(scratch + lay.masks_off);
+    mb.wcnt = reinterpret_cast<uint2*>(scratch + lay.wcnt_off);
+    mb.chunks = reinterpret_cast<uint2*>(scratch + lay.chunks_off);
+    mb.cross = reinterpret_cast<float*>(scratch + lay.cross_off);
+    mb.vertices = (float4*)d_vertices;
+    mb.quads = (uint4*)d_quads;
+    mb.ids = (uint4*)d_quad_ids;
+    mb.counts = (uint32_t*)d_counts;
+    mb.nodes = dev->d_nodes;
+    mb.n_mats = dev->n_mats;
+    // (plain copies: a launch takes the address of each argument)
+    uint64_t *bits = mb.bits, *masks = mb.masks;
+    uint2 *wcnt = mb.wcnt, *chunks = mb.chunks;
+    uint32_t* counts = mb.counts;
+    if (!mb.vertices) ml.max_vertices = 0u;
+    if (!mb.quads) ml.max_quads = 0u;
+    // the program in LDS where it fits (the walking kernels keep no per-wave scratch), as for the points
+    const size_t prog_bytes = (size_t)dev->n_recs * sizeof(WoRec);
+    const bool in_lds = prog_bytes <= kLdsBudget;
+    const size_t walk_lds = in_lds ? prog_bytes : 0;
+    hipStream_t stream = (hipStream_t)stream_v;
+    const size_t word_lanes = (size_t)lay.words * 64u, chunk_lanes = (size_t)lay.chunks * kBlock;
+    const int passes = mesh_passes();
+    {
+        void* args[] = {&dev->d_prog, &dev->n_recs, &ml, &bits};
+        if (query_launch(dev, in_lds ? (const void*)mesh_corners_kernel<true> : (const void*)mesh_corners_kernel<false>,
+                         walk_lds, word_lanes, args, stream, "mesh corner kernel launch", nullptr, err, errlen))
+            return -1;
+    }
+    if (passes < 2) return 0;
+    {
+        void* args[] = {&ml, &bits, &masks, &wcnt};
+        if (query_launch(dev, (const void*)mesh_count_kernel, 0, word_lanes, args, stream, "mesh count kernel launch",
+                         nullptr, err, errlen))
+            return -1;
+    }
+    if (passes < 3) return 0;
+    {
+        void* sums[] = {&ml, &wcnt, &chunks};
+        void* scan[] = {&ml, &chunks, &counts};
+        void* words[] = {&ml, &wcnt, &chunks};
+        if (query_launch(dev, (const void*)mesh_chunk_sums_kernel, 0, chunk_lanes, sums, stream,
+                         "mesh scan kernel launch", nullptr, err, errlen) ||
+            query_launch(dev, (const void*)mesh_scan_chunks_kernel, 0, kBlock, scan, stream, "mesh scan kernel launch",
+                         nullptr, err, errlen) ||
+            query_launch(dev, (const void*)mesh_scan_words_kernel, 0, chunk_lanes, words, stream,
+                         "mesh scan kernel launch", nullptr, err, errlen))
+            return -1;
+    }
+    if (passes < 4) return 0;
+    {
+        // the quads' number is the device's alone: a resident grid, whose loops end at the count
+        void* args[] = {&dev->d_prog, &dev->n_recs, &ml, &mb};
+        if (query_launch(dev, in_lds ? (const void*)mesh_edges_kernel<true> : (const void*)mesh_edges_kernel<false>,
+                         walk_lds, (size_t)lay.corners * 3u, args, stream, "mesh edge kernel launch", nullptr, err, errlen))
+            return -1;
+    }
+    if (passes < 5 || ml.max_vertices == 0u) return 0;
+    void* args[] = {&ml, &mb};
+    return query_launch(dev, (const void*)mesh_vertices_kernel, 0, word_lanes, args, stream, "mesh vertex kernel launch",
+                        nullptr, err, errlen);
+}
+
+extern "C" int wo_dev_mesh_host(WoDev* dev, WoMeshLaunch const* ml, void* vertices, void* quads, void* quad_ids,
+                                void* counts, char* err, size_t errlen) {
+    // the counts (one row), the scratch, then the vertex, quad and id rows
+    const size_t row = 16u, scratch = (wo_mesh_layout(ml->n).bytes + 15u) & ~(size_t)15u;
+    const size_t vbytes = vertices ? (size_t)ml->max_vertices * row : 0u, qbytes = quads ? (size_t)ml->max_quads * row : 0u;
+    const size_t ibytes = quads && quad_ids ? qbytes : 0u;
+    const size_t voff = row + scratch, qoff = voff + vbytes, ioff = qoff + qbytes;
+    return host_round_trip(
+        dev, ioff + ibytes, {}, "",
+        [&](char* io) {
+            return wo_dev_mesh(dev, ml, vbytes ? io + voff : nullptr, qbytes ? io + qoff : nullptr,
+                               ibytes ? io + ioff : nullptr, io, io + row, dev->stream, err, errlen);
+        },
+        {{counts, 0, row}, {vertices, voff, vbytes}, {quads, qoff, qbytes}, {quad_ids, ioff, ibytes}}, "mesh query", err,
+        errlen);
 }

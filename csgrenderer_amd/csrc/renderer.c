@@ -942,6 +942,73 @@ int wo_renderer_mass_properties(Wo_Renderer* r, Wo_MassGrid const* grid, Wo_Mass
     return wo_mass_properties_from_sums(grid, &sums, out);
 }
 
+/* surface mesh: the arguments are checked on the host (mesh.c) before the device is touched, so a
+ * device-less renderer reports a bad argument by its own message */
+int wo_renderer_mesh_device(Wo_Renderer* r, Wo_MeshGrid const* grid, Wo_MeshVertex* d_vertices, uint32_t max_vertices,
+                            Wo_MeshQuad* d_quads, Wo_MeshQuadIds* d_quad_ids, uint32_t max_quads,
+                            Wo_MeshCounts* d_counts, void* d_scratch, size_t scratch_bytes, void* stream) {
+    if (!r) return -1;
+    WoMeshLaunch ml;
+    if (wo_mesh_args_check(grid, d_vertices, max_vertices, d_quads, d_quad_ids, max_quads, d_counts, d_scratch,
+                           scratch_bytes, &ml))
+        return -1;
+    if (sync_device(r)) return -1;
+    char err[256] = {0};
+    if (wo_dev_mesh(r->dev, &ml, ml.max_vertices ? d_vertices : NULL, ml.max_quads ? d_quads : NULL,
+                    ml.max_quads ? d_quad_ids : NULL, d_counts, d_scratch, stream, err, sizeof err)) {
+        wo_set_error("mesh launch failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
+int wo_renderer_mesh(Wo_Renderer* r, Wo_MeshGrid const* grid, Wo_Mesh* out) {
+    if (!r) return -1;
+    WoMeshLaunch ml;
+    float h[3];
+    if (wo_mesh_grid_check(grid, h)) return -1;
+    if (!out) {
+        wo_set_error("mesh: NULL result");
+        return -1;
+    }
+    memset(out, 0, sizeof *out);
+    if (sync_device(r)) return -1;
+    for (int a = 0; a < 3; ++a) {
+        ml.lo[a] = grid->lo[a];
+        ml.h[a] = h[a];
+        ml.n[a] = grid->n[a];
+    }
+    ml.iters = grid->iters;
+    ml.max_vertices = ml.max_quads = 0u; /* the counts-only pass */
+    char err[256] = {0};
+    Wo_MeshCounts counts;
+    if (wo_dev_mesh_host(r->dev, &ml, NULL, NULL, NULL, &counts, err, sizeof err)) {
+        wo_set_error("mesh query failed: %s", err);
+        return -1;
+    }
+    if (counts.vertices == 0u && counts.quads == 0u) {
+        out->counts = counts;
+        return 0;
+    }
+    /* at least one row each, so a mesh with rows never carries a NULL array */
+    out->vertices = (Wo_MeshVertex*)malloc(((size_t)counts.vertices + 1u) * sizeof *out->vertices);
+    out->quads = (Wo_MeshQuad*)malloc(((size_t)counts.quads + 1u) * sizeof *out->quads);
+    out->quad_ids = (Wo_MeshQuadIds*)malloc(((size_t)counts.quads + 1u) * sizeof *out->quad_ids);
+    if (!out->vertices || !out->quads || !out->quad_ids) {
+        wo_mesh_free(out);
+        wo_set_error("mesh: out of memory for %u vertices and %u quads", counts.vertices, counts.quads);
+        return -1;
+    }
+    ml.max_vertices = counts.vertices;
+    ml.max_quads = counts.quads;
+    if (wo_dev_mesh_host(r->dev, &ml, out->vertices, out->quads, out->quad_ids, &out->counts, err, sizeof err)) {
+        wo_mesh_free(out);
+        wo_set_error("mesh query failed: %s", err);
+        return -1;
+    }
+    return 0;
+}
+
 /* first-hit feature buffers: every argument is checked before the device is touched, so a
  * device-less renderer reports a bad argument by its own message */
 _Static_assert(sizeof(Wo_FeatureIds) == 16, "a Wo_FeatureIds is one 16-byte row");

@@ -113,6 +113,46 @@ typedef struct WoMassLaunch {
 } WoMassLaunch;
 int wo_dev_mass_sums(WoDev* dev, WoMassLaunch const* ml, void* d_sums, void* stream, char* err, size_t errlen);
 int wo_dev_mass_sums_host(WoDev* dev, WoMassLaunch const* ml, void* sums, char* err, size_t errlen);
+/* Surface mesh of the solid (renderer_ext.h wo_renderer_mesh_device): what the kernels need of a
+ * checked Wo_MeshGrid (h as wo_mesh_grid_check gives it) and the caller's maxima. */
+typedef struct WoMeshLaunch {
+    float lo[3], h[3];
+    uint32_t n[3];
+    uint32_t iters, max_vertices, max_quads;
+} WoMeshLaunch;
+/* The scratch buffer's sections, byte offsets from its 16-byte aligned start, for a grid of
+ * n cells per axis: corners = (n0+1)(n1+1)(n2+1), words = 64 corners each, chunks = 1024 words
+ * each (WO_MESH_CHUNK_WORDS: the unit of the scan).  bits: one uint64 of inside bits per word;
+ * masks: four uint64 per word (active cell, taken x, y, z edge of the word's corners); wcnt:
+ * two uint32 per word (vertices, quads: counts, then exclusive prefixes); chunks: two uint32
+ * per chunk (likewise); cross: one float per corner and axis, written where the edge is taken. */
+#define WO_MESH_CHUNK_WORDS 1024u
+typedef struct WoMeshLayout {
+    uint64_t corners, words, chunks;
+    size_t bits_off, masks_off, wcnt_off, chunks_off, cross_off, bytes;
+} WoMeshLayout;
+static inline WoMeshLayout wo_mesh_layout(uint32_t const n[3]) {
+    WoMeshLayout l;
+    l.corners = (uint64_t)(n[0] + 1u) * (n[1] + 1u) * (n[2] + 1u);
+    l.words = (l.corners + 63u) / 64u;
+    l.chunks = (l.words + WO_MESH_CHUNK_WORDS - 1u) / WO_MESH_CHUNK_WORDS;
+    size_t off = 0;
+    l.bits_off = off, off += (size_t)l.words * 8u;
+    l.masks_off = off, off += (size_t)l.words * 32u;
+    l.wcnt_off = off, off += (size_t)l.words * 8u;
+    l.chunks_off = off, off += ((size_t)l.chunks * 8u + 15u) & ~(size_t)15u;
+    l.cross_off = off, off += ((size_t)l.corners * 12u + 15u) & ~(size_t)15u;
+    l.bytes = off;
+    return l;
+}
+/* Everything is device memory, 16-byte aligned and already checked (mesh.c wo_mesh_args_check);
+ * d_vertices / d_quads / d_quad_ids may be NULL as the maxima allow.  Async on `stream`; not a ray
+ * launch.  The host form runs the device form in the device's staging buffer: counts and scratch,
+ * then the max_vertices, max_quads and (ids != NULL) max_quads rows, copied back (synchronous). */
+int wo_dev_mesh(WoDev* dev, WoMeshLaunch const* ml, void* d_vertices, void* d_quads, void* d_quad_ids, void* d_counts,
+                void* d_scratch, void* stream, char* err, size_t errlen);
+int wo_dev_mesh_host(WoDev* dev, WoMeshLaunch const* ml, void* vertices, void* quads, void* quad_ids, void* counts,
+                     char* err, size_t errlen);
 /* First-hit feature buffers (renderer_ext.h wo_renderer_render_features_device): the
  * three planes of the rank's rows of `frame` into d_out (device memory, 16-byte
  * aligned; plane p of local pixel i is the 16-byte row p * plane_stride + i), async on

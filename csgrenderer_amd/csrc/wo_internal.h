@@ -122,6 +122,12 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
 /* present.c: binary PPM (RGB) of a B8G8R8A8 frame; 0 or -1 (last_error) */
 int wo_write_ppm_bgra8(char const* path, uint32_t const* bgra8, uint32_t w, uint32_t h);
 
+/* mesh.c: wo_renderer_mesh_device's argument checks in their stated order (no device is touched); on
+ * success *ml (may be NULL) is the launch: the grid, its cell sizes and the maxima (0 for a NULL buffer) */
+int wo_mesh_args_check(Wo_MeshGrid const* grid, void const* d_vertices, uint32_t max_vertices, void const* d_quads,
+                       void const* d_quad_ids, uint32_t max_quads, void const* d_counts, void const* d_scratch,
+                       size_t scratch_bytes, WoMeshLaunch* ml);
+
 /* renderer.c */
 void wo_set_error(char const* fmt, ...);
 double wo_monotonic_sec(void);

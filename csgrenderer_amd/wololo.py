@@ -160,6 +160,43 @@ class DenoiseParams(Structure):
 DENOISE_DEMODULATE, DENOISE_STOP_AT_NODES, DENOISE_MAX_LEVELS = 1, 2, 8
 assert ctypes.sizeof(DenoiseParams) == 24
 
+
+# renderer_ext.h Wo_MeshGrid ... Wo_Mesh (the closed quad mesh of the solid, surface nets on a uniform grid)
+class MeshGrid(Structure):
+    _fields_ = [("lo", c_float * 3), ("hi", c_float * 3), ("n", c_uint32 * 3), ("iters", c_uint32),
+                ("flags", c_uint32), ("reserved", c_uint32)]
+
+
+class MeshVertex(Structure):
+    _fields_ = [("p", c_float * 3), ("cell", c_uint32)]
+
+
+class MeshQuad(Structure):
+    _fields_ = [("v", c_uint32 * 4)]
+
+
+class MeshQuadIds(Structure):
+    _fields_ = [("leaf", c_uint32), ("node", c_uint32), ("material", c_uint32), ("flags", c_uint32)]
+
+
+class MeshCounts(Structure):
+    _fields_ = [("vertices", c_uint32), ("quads", c_uint32), ("cap_quads", c_uint32), ("flags", c_uint32)]
+
+
+class Mesh(Structure):
+    _fields_ = [("vertices", POINTER(MeshVertex)), ("quads", POINTER(MeshQuad)), ("quad_ids", POINTER(MeshQuadIds)),
+                ("counts", MeshCounts)]
+
+
+# numpy views of Wo_MeshVertex / Wo_MeshQuadIds arrays (Renderer.mesh returns them; quads are (n, 4) uint32)
+MESH_VERTEX_FIELDS = [("p", "<f4", (3,)), ("cell", "<u4")]
+MESH_QUAD_IDS_FIELDS = [("leaf", "<u4"), ("node", "<u4"), ("material", "<u4"), ("flags", "<u4")]
+MESH_MAX_CELLS, MESH_MAX_ITERS = 1024, 24
+MESH_TRUNCATED = 1  # Wo_MeshCounts.flags
+MESH_QUAD_AXIS, MESH_QUAD_POSITIVE, MESH_QUAD_CAP = 3, 4, 8  # Wo_MeshQuadIds.flags
+assert ctypes.sizeof(MeshGrid) == 48 and ctypes.sizeof(MeshCounts) == 16
+assert ctypes.sizeof(MeshVertex) == 16 and ctypes.sizeof(MeshQuad) == 16 and ctypes.sizeof(MeshQuadIds) == 16
+
 assert ctypes.sizeof(Ray) == 32 and ctypes.sizeof(RayHit) == 32
 assert ctypes.sizeof(RayCrossing) == 16 and ctypes.sizeof(RaySpans) == 16
 assert ctypes.sizeof(Vec3) == 24 and ctypes.sizeof(Quaternion) == 32 and ctypes.sizeof(NodeArgument) == 64
@@ -255,6 +292,13 @@ SIGNATURES = {
     "wo_denoise_host": (c_int, [POINTER(DenoiseParams), c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "wo_renderer_render_denoised": (c_int, [c_void_p, POINTER(RenderParams), POINTER(DenoiseParams), c_void_p]),
+    "wo_mesh_grid_check": (c_int, [POINTER(MeshGrid), POINTER(c_float)]),
+    "wo_mesh_scratch_bytes": (c_size_t, [POINTER(MeshGrid)]),
+    "wo_renderer_mesh_device": (c_int, [c_void_p, POINTER(MeshGrid), c_void_p, c_uint32, c_void_p, c_void_p, c_uint32,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wo_renderer_mesh": (c_int, [c_void_p, POINTER(MeshGrid), POINTER(Mesh)]),
+    "wo_mesh_free": (None, [POINTER(Mesh)]),
+    "wo_mesh_write_obj": (c_int, [c_char_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]),
     "wo_renderer_set_jit_async": (None, [c_void_p, c_int]),
     "wo_renderer_jit_pending": (c_int, [c_void_p]),
     "wo_renderer_prepare": (c_int, [c_void_p]),
@@ -595,6 +639,41 @@ class Renderer:
             raise WololoError(last_error())
         return props, sums
 
+    # ---- surface mesh of the solid (renderer_ext.h wo_renderer_mesh ...) ----
+    def mesh(self, grid: MeshGrid):
+        """The closed quad mesh of the solid clipped to the grid's box: (vertices[V] of
+        MESH_VERTEX_FIELDS, quads (Q, 4) uint32, ids[Q] of MESH_QUAD_IDS_FIELDS, MeshCounts).
+        Synchronous; the arrays are copies, the library's own are released."""
+        import numpy as np
+        m = Mesh()
+        if self.lib.wo_renderer_mesh(self.ptr, ctypes.byref(grid) if grid is not None else None, ctypes.byref(m)):
+            raise WololoError(last_error())
+        try:
+            nv, nq = int(m.counts.vertices), int(m.counts.quads)
+            vertices = np.zeros(nv, dtype=np.dtype(MESH_VERTEX_FIELDS))
+            quads = np.zeros((nq, 4), dtype=np.uint32)
+            ids = np.zeros(nq, dtype=np.dtype(MESH_QUAD_IDS_FIELDS))
+            if nv:
+                ctypes.memmove(vertices.ctypes.data, m.vertices, 16 * nv)
+            if nq:
+                ctypes.memmove(quads.ctypes.data, m.quads, 16 * nq)
+                ctypes.memmove(ids.ctypes.data, m.quad_ids, 16 * nq)
+            counts = MeshCounts(m.counts.vertices, m.counts.quads, m.counts.cap_quads, m.counts.flags)
+        finally:
+            self.lib.wo_mesh_free(ctypes.byref(m))
+        return vertices, quads, ids, counts
+
+    def mesh_device(self, grid: MeshGrid, d_vertices: int, max_vertices: int, d_quads: int, d_quad_ids: int,
+                    max_quads: int, d_counts: int, d_scratch: int, scratch_bytes: int, stream: int = 0):
+        """The mesh into device memory (16-byte rows at d_vertices, d_quads and, unless 0, d_quad_ids;
+        the Wo_MeshCounts at d_counts), asynchronously on `stream`; d_scratch holds at least
+        mesh_scratch_bytes(grid) bytes.  With both maxima 0 only the counts are made."""
+        if self.lib.wo_renderer_mesh_device(self.ptr, ctypes.byref(grid) if grid is not None else None,
+                                            c_void_p(d_vertices or None), int(max_vertices), c_void_p(d_quads or None),
+                                            c_void_p(d_quad_ids or None), int(max_quads), c_void_p(d_counts or None),
+                                            c_void_p(d_scratch or None), int(scratch_bytes), c_void_p(stream or None)):
+            raise WololoError(last_error())
+
     # ---- first-hit feature buffers (renderer_ext.h wo_renderer_render_features ...) ----
     def render_features(self, params: RenderParams):
         """The feature planes of a PATHTRACE frame: (albedo (H, W, 4) float32 with w = coverage,
@@ -864,6 +943,45 @@ def mass_properties_from_sums(grid: MassGrid, sums: MassSums) -> MassProperties:
     if load().wo_mass_properties_from_sums(ctypes.byref(grid), ctypes.byref(sums), ctypes.byref(props)):
         raise WololoError(last_error())
     return props
+
+
+def mesh_grid(lo, hi, n, iters: int = 16) -> MeshGrid:
+    """A Wo_MeshGrid over the clip box [lo, hi] with n = (n0, n1, n2) cells (or one count for all three)."""
+    g = MeshGrid()
+    g.lo[:] = [float(x) for x in lo]
+    g.hi[:] = [float(x) for x in hi]
+    g.n[:] = [int(n)] * 3 if isinstance(n, int) else [int(x) for x in n]
+    g.iters = int(iters)
+    return g
+
+
+def mesh_grid_check(grid: MeshGrid):
+    """wo_mesh_grid_check (host only): the cell sizes h[3] of a good grid; raises for a bad one."""
+    h = (c_float * 3)()
+    if load().wo_mesh_grid_check(ctypes.byref(grid) if grid is not None else None, h):
+        raise WololoError(last_error())
+    return [float(x) for x in h]
+
+
+def mesh_scratch_bytes(grid: MeshGrid) -> int:
+    """Bytes of device scratch wo_renderer_mesh_device needs; raises for a bad grid (the C call returns 0)."""
+    n = int(load().wo_mesh_scratch_bytes(ctypes.byref(grid) if grid is not None else None))
+    if n == 0:
+        raise WololoError(last_error())
+    return n
+
+
+def write_obj(path: str, vertices, quads, ids=None):
+    """wo_mesh_write_obj on numpy arrays as Renderer.mesh returns them (ids None: one ungrouped list of faces)."""
+    import numpy as np
+    v = np.ascontiguousarray(vertices, dtype=np.dtype(MESH_VERTEX_FIELDS))
+    q = np.ascontiguousarray(quads, dtype=np.uint32).reshape(-1, 4)
+    i = None if ids is None else np.ascontiguousarray(ids, dtype=np.dtype(MESH_QUAD_IDS_FIELDS))
+    if i is not None and len(i) != len(q):
+        raise ValueError("ids: one row per quad")
+    if load().wo_mesh_write_obj(os.fsencode(path), v.ctypes.data_as(c_void_p), len(v), q.ctypes.data_as(c_void_p),
+                                i.ctypes.data_as(c_void_p) if i is not None else None, len(q)):
+        raise WololoError(last_error())
 
 
 JIT_ORIGINS = ("process", "disk", "compiled")

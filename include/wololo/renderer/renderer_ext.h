@@ -583,6 +583,104 @@ int wo_denoise_host(Wo_DenoiseParams const* dp, uint32_t width, uint32_t height,
 int wo_renderer_render_denoised(Wo_Renderer* r, Wo_RenderParams const* params, Wo_DenoiseParams const* dp_or_null,
                                 float* out_rgba);
 
+/* ---- surface mesh of the solid (naive surface nets on a uniform grid) ----
+ * The solid itself, clipped to a box, as a closed quad mesh: one vertex per grid cell the
+ * surface passes through, one quad per grid edge it crosses.  Everything is defined by point
+ * classification (above: BOUND records ignored), every operation is fp32 and rounded once,
+ * nothing is contracted, the division is correctly rounded; the order of every row is fixed,
+ * so nothing depends on launch geometry and a CPU restatement matches bit for bit.
+ *
+ * Grid.  h[a] = (hi[a] - lo[a]) / (float)n[a].  Corner (i, j, k), 0 <= i <= n[0] and likewise
+ * j, k, has coordinate c_a(i) = lo[a] + (float)i * h[a] (a product, then a sum).  Corners are
+ * numbered (k (n1+1) + j)(n0+1) + i, cells (k n1 + j) n0 + i.  wo_mesh_grid_check returns -1
+ * with wo_renderer_last_error naming the first failing check, in this order: a NULL grid; a
+ * non-finite bound; lo >= hi; a count outside 2 .. WO_MESH_MAX_CELLS; iters > 24; flags != 0;
+ * reserved != 0; a non-finite h, or h <= 0.  Host arithmetic, no device needed.
+ *
+ * Inside.  A corner is inside iff it is not on the grid's outermost layer (0 < i < n[0],
+ * likewise j and k) and point classification calls it WO_POINT_INSIDE.  So the mesh is that of
+ * the solid clipped to the box: an unbounded half-space, or a solid cut by a face of the box,
+ * is closed there by cap quads.
+ *
+ * Crossing of a grid edge.  The edge along axis a from corner C to C + e_a is taken when the
+ * two inside bits differ.  ta = c_a(C), tb = c_a(C + e_a), sa = the inside bit of C; `iters`
+ * times: tm = 0.5f * (ta + tb); sm = the plain classification (nothing forced: the point is
+ * not a corner) of the edge's point with coordinate a replaced by tm; sm == sa sets ta = tm,
+ * else tb = tm.  The crossing is x = 0.5f * (ta + tb).
+ *
+ * Ids of that edge's quad.  A = the plain classification at the final ta, B at the final tb.
+ * A == B (only possible when the outside end is a forced corner): a cap, leaf = node =
+ * material = 0xFFFFFFFF and WO_MESH_QUAD_CAP.  Otherwise leaf is the first leaf record, in
+ * program order, whose own test (v <= f[3], as point classification states it) differs between
+ * the two points -- one exists, the root being a function of the leaf tests -- and node and
+ * material are that leaf's as in Wo_RayHit.  Coincident surfaces are thereby decided by record
+ * order.  flags = a | WO_MESH_QUAD_POSITIVE (sa set) | WO_MESH_QUAD_CAP.
+ *
+ * Vertices.  A cell with any of its 12 edges taken is active and gets one vertex; vertices are
+ * ordered by cell number, which vertex.cell holds.  Per coordinate the position is a sum from
+ * +0, in this order: a = 0, 1, 2 with u = (a+1)%3, v = (a+2)%3; dv = 0, 1; du = 0, 1; the edge
+ * along a from the cell's corner offset by du e_u + dv e_v, if taken, adds the point whose
+ * coordinate a is the crossing and whose u and v are that corner's.  Then each sum is divided
+ * by (float)count.
+ *
+ * Quads.  One per taken edge, ordered by (corner number of the lower corner) * 3 + a.  With the
+ * lower corner's cell coordinates as origin the four cells are at (u, v) offsets (-1,-1),
+ * (0,-1), (0,0), (-1,0) (all exist: a taken edge has an interior end); v[0..3] holds their
+ * vertex indices in that order when the lower corner is inside (the normal points along +a),
+ * else reversed.  The surface is closed and faces outward: every directed edge p->q of the
+ * quads occurs exactly as often as q->p.
+ *
+ * Counts and truncation.  d_counts always gets the full counts; rows >= max_* are not written;
+ * indices always use the full numbering; WO_MESH_TRUNCATED is set when either maximum was
+ * exceeded.  With max_vertices == 0 && max_quads == 0 the three buffers may be NULL: the
+ * counting passes and the edge pass (cap_quads is its count) run, nothing is emitted. */
+#define WO_MESH_MAX_CELLS 1024u
+#define WO_MESH_MAX_ITERS 24u
+typedef struct Wo_MeshGrid {      /* 48 bytes */
+    float lo[3], hi[3];           /* clip box: finite, lo < hi on every axis */
+    uint32_t n[3];                /* cells per axis, 2 .. WO_MESH_MAX_CELLS */
+    uint32_t iters;               /* bisection steps per crossing edge, 0 .. 24 */
+    uint32_t flags;               /* none defined: must be 0 */
+    uint32_t reserved;            /* 0 */
+} Wo_MeshGrid;
+typedef struct Wo_MeshVertex { float p[3]; uint32_t cell; } Wo_MeshVertex;     /* 16 bytes */
+typedef struct Wo_MeshQuad   { uint32_t v[4]; } Wo_MeshQuad;                   /* 16 bytes */
+typedef struct Wo_MeshQuadIds { uint32_t leaf; Wo_Node node; Wo_Material material; uint32_t flags; } Wo_MeshQuadIds; /* 16 bytes */
+typedef struct Wo_MeshCounts { uint32_t vertices, quads, cap_quads, flags; } Wo_MeshCounts;  /* 16 bytes */
+#define WO_MESH_TRUNCATED     1u  /* counts.flags: vertices > max_vertices or quads > max_quads */
+#define WO_MESH_QUAD_AXIS     3u  /* ids.flags & 3: axis of the grid edge the quad is dual to */
+#define WO_MESH_QUAD_POSITIVE 4u  /* the edge's lower corner is inside: the quad faces +axis */
+#define WO_MESH_QUAD_CAP      8u  /* the quad closes the solid at the clip box, no leaf */
+
+/* The checks above; h_out (may be NULL) gets the three cell sizes of a good grid. */
+int wo_mesh_grid_check(Wo_MeshGrid const* grid, float h_out[3]);
+/* Bytes of device scratch wo_renderer_mesh_device needs: about 12.7 bytes per corner (one
+ * inside bit, four mask bits and a count per corner, one crossing per edge).  0 for a bad grid. */
+size_t wo_mesh_scratch_bytes(Wo_MeshGrid const* grid);
+/* The mesh into DEVICE memory: asynchronous on `stream`, on the renderer's device only, ordered
+ * and uploaded as wo_renderer_trace_rays_device (an edited scene is compiled and uploaded
+ * first).  Allocates nothing and never waits for the host.  Every buffer is 16-byte aligned;
+ * d_quad_ids may be NULL; d_scratch holds at least wo_mesh_scratch_bytes(grid) bytes (more is
+ * accepted, only that many are used) and must not overlap an output.  -1 with
+ * wo_renderer_last_error, checked in this order before the device is touched: the grid (as
+ * wo_mesh_grid_check); a NULL d_counts or d_scratch; a NULL d_vertices with max_vertices > 0 or
+ * a NULL d_quads with max_quads > 0; a misaligned buffer; short scratch; then a device-less
+ * renderer.  wo_renderer_ray_path is left as it was, as by point classification. */
+int wo_renderer_mesh_device(Wo_Renderer* r, Wo_MeshGrid const* grid, Wo_MeshVertex* d_vertices, uint32_t max_vertices,
+                            Wo_MeshQuad* d_quads, Wo_MeshQuadIds* d_quad_ids, uint32_t max_quads,
+                            Wo_MeshCounts* d_counts, void* d_scratch, size_t scratch_bytes, void* stream);
+typedef struct Wo_Mesh { Wo_MeshVertex* vertices; Wo_MeshQuad* quads; Wo_MeshQuadIds* quad_ids; Wo_MeshCounts counts; } Wo_Mesh;
+/* The whole mesh into HOST arrays the library allocates (synchronous): a counts-only pass, the
+ * allocation, then the full pass, through the renderer's staging buffer and stream.  Release
+ * the arrays with wo_mesh_free, which leaves NULLs and zero counts. */
+int wo_renderer_mesh(Wo_Renderer* r, Wo_MeshGrid const* grid, Wo_Mesh* out);
+void wo_mesh_free(Wo_Mesh* mesh);
+/* Wavefront OBJ of a mesh in host memory (pure host code): "v" lines with %.9g (a float
+ * round-trips), "f" lines of 1-based quads.  With ids the faces are grouped "g node_<id>" in
+ * ascending node order, then "g cap"; quad order is kept inside a group.  0, or -1 (last_error). */
+int wo_mesh_write_obj(char const* path, Wo_MeshVertex const* vertices, uint32_t n_vertices, Wo_MeshQuad const* quads,
+                      Wo_MeshQuadIds const* ids_or_null, uint32_t n_quads);
+
 /* Path-tracer kernel selection (results are identical; only speed differs).
  *   AUTO         union-only scenes of more than WOLOLO_LANES_MIN_PRIMS (256)
  *                primitives -> LANES; else scenes of up to WOLOLO_JIT_MAX_PRIMS
@@ -679,7 +777,8 @@ void wo_renderer_clear_error(void);
  * compiled, for the value types of the C ABI (Wo_Vec3, Wo_Quaternion,
  * Wo_Node_Argument, Wo_RenderParams, WoRec, WoMaterial, WoCamera, WoFrame, Wo_Ray, Wo_RayHit,
  * Wo_RayCrossing, Wo_RaySpans, Wo_MassGrid, Wo_MassPlan, Wo_MassSums, Wo_MassProperties,
- * Wo_FeatureIds, Wo_DenoiseParams);
+ * Wo_FeatureIds, Wo_DenoiseParams, Wo_MeshGrid, Wo_MeshVertex, Wo_MeshQuad, Wo_MeshQuadIds, Wo_MeshCounts,
+ * Wo_Mesh);
  * (size_t)-1 for an unknown name.  Bindings check their mirrors with it. */
 size_t wo_abi_layout(char const* type, char const* field);
 /* Device self-check of the path tracer's fast correctly rounded square root
