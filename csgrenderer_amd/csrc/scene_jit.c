@@ -115,9 +115,10 @@ typedef struct Gen {
     uint32_t nterm, term_bit0;
     struct TEnt *tgroups, *tterms;
     /* the sky-ray predicate is being written (gen_sky_rays): a lane's own tests, so no
-     * wave-level member skip (a met interval only narrows: the same emptiness); 2 at the
-     * levels that test a literal by one member alone (gen_sky_term), `sky_only` then
-     * naming the member gen_members writes (kSkyAll: every member) */
+     * wave-level member skip (a met interval only narrows: the same emptiness); 2 and 3 at
+     * the levels that test a literal by one member alone (gen_sky_term), `sky_only` then
+     * naming the member gen_members writes (kSkyAll: every member); 3 tests a sphere member
+     * by sphere_reaches */
     int sky;
     uint32_t sky_only;
     int err;
@@ -911,9 +912,14 @@ static void gen_term_body(Gen* g, const SPrim* q, int indent) {
  * empty or ending behind the origin -- or else the face pair of the box's thinnest axis
  * (csg32's slab: 0.5 against 12 x 12), written by gen_members with the same reach
  * condition.  One reciprocal instead of three and no square root: 14 short tests, which
- * the kernel holds in the registers it had (58 VGPRs, no scratch). */
+ * the kernel holds in the registers it had (58 VGPRs, no scratch).
+ * Level 4 is level 3 with each sphere member tested by sphere_reaches instead: also gone
+ * where the far root the trace would compute is surely <= t_min, the reach condition the
+ * face pair already carries.  A ray that scatters off a sphere starts on its surface,
+ * where disc ~ b^2 and sphere_need always holds; level 3 accepts no such ray.  One more
+ * VALU a sphere test (wo_device_common.h states the bound). */
 
-#define JIT_SKY_LEVELS 3
+#define JIT_SKY_LEVELS 4
 /* the smallest sphere among the members of the convex primitive at pc, or kSkyAll */
 static uint32_t sky_sphere_member(const Gen* g, uint32_t pc) {
     uint32_t best = kSkyAll;
@@ -951,15 +957,16 @@ static int gen_sky_term(Gen* g, const SPrim* q, int indent) {
     if (!pos0) return 0;
     const WoRec* P = &g->prog[pc0];
     bput(g->b, "%*s{  // a term on its own: primitive %u\n", indent, "", P->u1);
-    /* the sphere tested alone: a lone sphere's, at level 3 the smallest of any first literal */
+    /* the sphere tested alone: a lone sphere's, from level 3 the smallest of any first literal */
     uint32_t ms = q->npc == 1u && P->u0 == 1u && g->prog[pc0 + 1u].op == WO_LEAF_SPHERE ? 0u : kSkyAll;
-    if (g->sky == 2) ms = sky_sphere_member(g, pc0);
+    if (g->sky >= 2) ms = sky_sphere_member(g, pc0);
     if (ms != kSkyAll) {
         put_lone_disc(g, &g->prog[pc0 + 1u + ms], indent);
-        bput(g->b, "%*s  gone = gone & !wodev::sphere_need(b, disc);\n%*s}\n", indent, "", indent, "");
+        bput(g->b, "%*s  gone = gone & !wodev::%s(b, disc);\n%*s}\n", indent, "",
+             g->sky == 3 ? "sphere_reaches" : "sphere_need", indent, "");
         return 1;
     }
-    if (g->sky == 2) g->sky_only = sky_thin_pair(g, pc0); /* kSkyAll where it has none: every member */
+    if (g->sky >= 2) g->sky_only = sky_thin_pair(g, pc0); /* kSkyAll where it has none: every member */
     bput(g->b, "%*s  wodev::Ivl ia;\n", indent, "");
     gen_term_ivl(g, pc0, "ia", indent + 2);
     g->sky_only = kSkyAll;
@@ -1012,7 +1019,7 @@ static int gen_sky_rays(Gen* g, int level) {
     Buf body = {0};
     Buf* keep = g->b;
     g->b = &body;
-    g->sky = level >= 3 ? 2 : 1;
+    g->sky = level >= 4 ? 3 : level >= 3 ? 2 : 1;
     int ok = 1;
     for (uint32_t i = 0; i < g->ntunb && ok; ++i) ok = gen_sky_term(g, &g->tunb[i], 4);
     ok = ok && gen_sky_spatial(g, p, g->nsprims, 4, 1, level);
@@ -2699,7 +2706,8 @@ char* wo_generate_jit_source(WoRec const* prog, uint32_t n_recs, uint32_t n_prim
     }
     /* the sharpest level the scene has by default (csg32, 1920x1080x64: 2.428 ms without
      * the predicate, 2.413 at level 1, 2.369 at level 2, profiles/sky_rays_ab.txt; later
-     * 2.249 at level 2 against 2.139 at level 3, profiles/sky_rays_terms_ab.txt) */
+     * 2.249 at level 2 against 2.139 at level 3, profiles/sky_rays_terms_ab.txt; 2.131 at
+     * level 3 against 2.083 at level 4, profiles/sky_rays_reach_ab.txt) */
     int sky_default = 0;
     while (sky_default < JIT_SKY_LEVELS && sky[sky_default].s) ++sky_default;
     if (have_sky)

@@ -32,6 +32,9 @@ with a lane that goes on and ends no path (probes 10..13), counted apart for cam
 iterations; and it counts the bounce iterations that run once the tile's jobs are drained.
 
     python tools/sky_ray_share.py --terms-probe --levels 2,3 --out profiles/sky_rays_terms_before.txt
+    python tools/sky_ray_share.py --terms-probe --levels 3,4 --out profiles/sky_rays_reach_before.txt
+
+--levels takes every level the scene has (csg32: 1 to 4), in --terms-probe, --ab and --cpu.
 """
 import argparse
 import os
@@ -45,19 +48,31 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def cpu_share(say, n_cam):
-    """The predicate on the host against the oracle (the test's harness)."""
+def cpu_share(say, n_cam, levels):
+    """The predicate on the host against the oracle (the test's harness; a level it does not
+    build itself, 3 or 4, from the same translation unit)."""
+    import ctypes
     import pathlib
+    import subprocess
     import tempfile
 
     import numpy as np
     import test_sky_rays as t
 
-    built = t.build_harness(pathlib.Path(tempfile.mkdtemp(prefix="sky_rays")))
+    tmp = pathlib.Path(tempfile.mkdtemp(prefix="sky_rays"))
+    built = t.build_harness(tmp)
+    levels = [L for L in levels if L > 0]
     for scene in t.SCENES:
         s = built[scene]
+        for level in levels:
+            if level not in s["libs"]:
+                so = tmp / f"{scene}_{level}.so"
+                subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-fopenmp", "-shared", "-fPIC",
+                                f"-DWO_SKY_RAYS={level}", "-I", os.path.join(ROOT, "include"), "-o", str(so),
+                                str(tmp / f"{scene}.cpp")], check=True)
+                s["libs"][level] = ctypes.CDLL(str(so))
         o, d = t._scattered(s, np.random.default_rng(1), n_cam)
-        for level in t.LEVELS:
+        for level in levels:
             pred, hit, _ = t._check(s, level, o, d)
             say(f"cpu {scene} level {level}: {len(o)} scattered rays, {100.0 * (~hit).mean():.1f} % hit nothing, "
                 f"predicate accepts {100.0 * pred.mean():.1f} %, accepted rays with a hit: {int((pred & hit).sum())}")
@@ -227,7 +242,7 @@ def main():
                 r.close()
     if a.cpu:
         os.environ.setdefault("WOLOLO_ALLOW_NO_DEVICE", "1")
-        cpu_share(say, a.cpu_rays)
+        cpu_share(say, a.cpu_rays, levels)
     if a.out:
         open(a.out, "w").write("\n".join(lines) + "\n")
 
